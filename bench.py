@@ -18,12 +18,19 @@ scaling: weak (default).  Every rank encodes its own 1M-row shard (rows are
 value  : GT bytes of all ranks / (max over ranks of the timed wall time).
 
 Also printed: `roofline` for the dominant kernel k_encode (algorithmic bytes
-= line bytes read + record bytes written, per launch / its HIP-event time)
-and `cpu_baseline`: the reference's own `main compress` (oracle/_ref/main,
-compiled from the reference sources; single-threaded) on a bounded sample of
-the same rows, timed on this host.
+= line bytes read + record bytes written, per launch / its HIP-event time,
+taken inside the timed steps).
 
-Run: python bench.py [--gpus N --steps K --warmup W]; for N > 1 under
+A plain run sets up, warms up, times the K steps and prints the line.
+--full adds what takes runs of its own: `cpu_baseline`, the reference's own
+`main compress` (oracle/_ref/main, compiled from the reference sources;
+single-threaded) on a bounded sample of the same rows, timed on this host and
+compared with the GPU's records, and the roofline's measured device-copy rate
+(`measured_torch_copy_gbs`, null without --full).  The CPU baselines of the
+other --mode rows need --full as well.
+--dump-outputs DIR writes what the last timed step computed (dump_outputs).
+
+Run: python bench.py [--gpus N --steps K --warmup W] [--full]; for N > 1 under
 torch.distributed.run (one process per GPU, RCCL).
 """
 import argparse
@@ -57,7 +64,14 @@ def parse():
                     help="--gpus N > 1, weak scaling: skip the strong-split sub-measurement")
     ap.add_argument("--cpu-rows", type=int, default=None,
                     help="rows in the CPU-baseline sample (default: about 1.2 GB of lines)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU baseline out")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, run what the line's secondary figures need: the CPU baseline "
+                         "(reference CLI or its restatement) with its output comparison, and the measured "
+                         "device-copy rate of the roofline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="--mode encode/biobank: after the timed steps write what the last step computed (record "
+                         "bytes, record offsets, error word) as DIR/<name>.npy, at most 64 MB in all")
     ap.add_argument("--verify-rows", type=int, default=64, help="rows checked against the CPU path")
     ap.add_argument("--mode", choices=["encode", "biobank", "decode", "query", "ingest", "devfile", "sparse",
                                        "distfile"],
@@ -89,6 +103,10 @@ def parse():
     ap.add_argument("--ingest-rows", type=int, default=200_000, help="rows of the --mode ingest file")
     ap.add_argument("--query-frac", type=float, default=0.125, help="rows selected by the --mode query range")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.dump_outputs and (a.mode not in ("encode", "biobank") or a.rows_total):
+        ap.error("--dump-outputs applies to --mode encode and to the one-batch --mode biobank")
     big = a.mode == "biobank"
     if a.samples is None:
         a.samples = 100_000 if big else 2504
@@ -292,6 +310,38 @@ def timed(torch, dev, args, step):
     return time.perf_counter() - t0, e0.elapsed_time(e1) / args.steps
 
 
+DUMP_SEED = 20240229   # the sample positions of --dump-outputs (fixed: two builds dump the same positions)
+
+
+def dump_sample(torch, t, max_elems, dtype, seed):
+    """t (1-D device tensor) as a host array of `dtype`: whole when it has at
+    most max_elems elements, else its values at max_elems sorted positions
+    drawn from (seed, len(t)) -- the same positions in every run and build."""
+    import numpy as np
+    if t.numel() > max_elems:
+        idx = np.sort(np.random.default_rng(seed).integers(0, t.numel(), max_elems, dtype=np.int64))
+        t = t[torch.from_numpy(idx).to(t.device)]
+    return t.cpu().numpy().astype(dtype)
+
+
+def dump_outputs(dirpath, torch, n, out, rec, err, rank, world):
+    """--dump-outputs: what a caller of the encode step receives, as the last
+    timed step left it: the record bytes out[0 : rec[n]] (float32), the record
+    offsets rec[0 : n+1] (float64, exact below 2^53) and the error word
+    (float64; -1 = no row error).  At most 40 MB + 16 MB + 8 bytes: a larger
+    array is sampled at fixed seeded positions (dump_sample).  With N > 1
+    ranks every rank writes its own files, <name>_rank<r>.npy."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    sfx = "" if world == 1 else "_rank%d" % rank
+    arrays = {"records": dump_sample(torch, out[:int(rec[n].item())], 10_000_000, np.float32, DUMP_SEED),
+              "record_offsets": dump_sample(torch, rec[:n + 1], 2_000_000, np.float64, DUMP_SEED + 1),
+              "row_error": err.cpu().numpy().astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirpath, name + sfx + ".npy"), a)
+    return {name + sfx: list(a.shape) for name, a in arrays.items()}
+
+
 def bench_decode(args, torch, vcfc, workload):
     """Row f1: decode the same synthetic batch (device-resident records made
     by the GPU encoder) back to VCF lines; every output byte is checked
@@ -332,7 +382,7 @@ def bench_decode(args, torch, vcfc, workload):
                         "traffic": load_pmc("%s/%dx%d" % (law_name(args.law), S, n), "pmc_k_dec.json"),
                         "algorithmic_bytes_per_launch": alg, "avg_launch_ms": round(ev_ms, 4)},
            "output_identical_to_input_rows": identical}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         dt, k, kind = cpu_reference_run(rows, recs, rec, args, lambda p: ["decompress", p, p + ".vcf"])
         res["cpu_baseline"] = {"value": round(4 * S * k / dt / 1e9, 4), "unit": "GB/s", "cores": 1, "kind": kind,
                                "sample": "`main decompress` of the first %d records (%d GT bytes), wall time %.2f s"
@@ -404,7 +454,7 @@ def bench_query(args, torch, vcfc, workload):
                                             "pmc_k_query.json"),
                         "algorithmic_bytes_per_launch": alg, "avg_launch_ms": round(ev_ms, 4)},
            "output_identical_to_selected_rows": identical}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         k = min(args.cpu_rows, n)
         ka = int(k * (0.5 - args.query_frac / 2))
         kb = min(k - 1, ka + max(1, int(k * args.query_frac)) - 1)
@@ -477,7 +527,7 @@ def bench_ingest(args, torch, vcfc, workload):
                             "unit": "GB/s", "frac": round(in_bytes * args.steps / elapsed / 1e9 / h2d, 4),
                             "traffic": None, "peak_note": "pinned H2D of this box, measured"},
                "output_identical_to_gpu_records": identical}
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             k = min(args.cpu_rows, n)
             end = int(rows.line_off[k].item()) if k < n else rows.total_bytes
             with open(os.path.join(tmp, "s.vcf"), "wb") as f:
@@ -625,7 +675,7 @@ def bench_sparse(args, torch, vcfc, workload):
                             "vcfc_bytes_per_sec": round((len(header) + rec_bytes) / t_sp / 1e9, 4)},
                "roofline": None, "roofline_note": "host-I/O bound: one pread (query) / pwritev (sparsify) per record",
                "output_identical_to_selected_rows": identical}
-        if not args.no_cpu_baseline and os.path.exists(ref):
+        if args.full and not args.no_cpu_baseline and os.path.exists(ref):
             with open(os.path.join(tmp, "r.out"), "wb") as so:
                 t0 = time.perf_counter()
                 r = subprocess.run([ref, "sparse-query", sp, q], stdout=so, stderr=subprocess.PIPE)
@@ -1178,7 +1228,8 @@ def main():
         e = int(err.cpu().numpy().view(np.uint64)[0])
         if e != vcfc.NO_ERROR:
             raise RuntimeError("encode reported row error %x" % e)
-        return dict(elapsed=elapsed, stages=stages, calls=calls, deferred=deferred, rows=rows, out=out, rec=rec)
+        return dict(elapsed=elapsed, stages=stages, calls=calls, deferred=deferred, rows=rows, out=out, rec=rec,
+                    err=err)
 
     if args.scaling == "strong":
         # the --rows rows of the N=1 line's dataset split over the ranks: each
@@ -1196,7 +1247,8 @@ def main():
     elapsed, stages, calls, deferred = P["elapsed"], P["stages"], P["calls"], P["deferred"]
     rows, out, rec = P["rows"], P["out"], P["rec"]
 
-    copy_gbs = measured_copy_gbs(torch, dev)
+    dumped = dump_outputs(args.dump_outputs, torch, n, out, rec, P["err"], rank, world) if args.dump_outputs else None
+    copy_gbs = measured_copy_gbs(torch, dev) if args.full else None   # (a run of its own: 5 x 4 GiB copies)
     out_bytes = int(rec[n].item())
     ms_step = elapsed * 1e3 / args.steps
     gt = torch.tensor([rows.gt_bytes], dtype=torch.int64, device=cdev)
@@ -1239,6 +1291,8 @@ def main():
            "roofline": roof}
     if rehearsal and args.rows != rows_asked:
         res["config"]["rehearsal_rows_per_rank"] = args.rows
+    if dumped is not None:
+        res["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     if world > 1 and args.mode == "encode" and args.scaling == "weak" and not args.no_strong:
         # BASELINE's metric is one fixed 2504 x 1M dataset on 1/2/4/8 GPUs:
         # the same ranks, in the same process group, then time the strong
@@ -1252,7 +1306,7 @@ def main():
         per_rank = gather_ints(torch, dist, cdev, world, [ns, Q["rows"].gt_bytes, int(Q["rec"][ns].item())])
         res["strong"] = strong_summary(per_rank, Q["elapsed"], args.steps,
                                        Q["stages"]["k_encode"] / max(Q["calls"], 1), rows_asked, law_name(args.law))
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cb, cpu_out, k = cpu_baseline(rows, torch, args)
         res["cpu_baseline"] = cb
         gpu_out = out[:int(rec[k].item())].cpu().numpy().tobytes()

@@ -96,6 +96,55 @@ def test_strong_summary():
         raise AssertionError("lost rows accepted")
 
 
+def test_plain_run_is_lean_and_full_is_an_option(monkeypatch):
+    """A plain run asks for none of the secondary measurements; --full turns
+    them on; --steps is at least one timed step; --dump-outputs belongs to the
+    encode step."""
+    import pytest
+    import bench
+
+    def parse(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + list(argv))
+        return bench.parse()
+    a = parse("--gpus", "1", "--steps", "7", "--warmup", "2")
+    assert (a.full, a.dump_outputs, a.steps, a.warmup, a.mode) == (False, None, 7, 2, "encode")
+    a = parse("--full", "--dump-outputs", "d")
+    assert a.full is True and a.dump_outputs == "d" and a.no_cpu_baseline is False
+    for bad in (["--steps", "0"], ["--warmup", "-1"], ["--mode", "decode", "--dump-outputs", "d"],
+                ["--mode", "biobank", "--rows-total", "5000000", "--dump-outputs", "d"]):
+        with pytest.raises(SystemExit):
+            parse(*bad)
+
+
+def test_dump_outputs_files(tmp_path):
+    """--dump-outputs: records / offsets / error word as float32 / float64
+    .npy; an array over its budget is sampled at positions that depend only on
+    the seed and its length, so two runs (or builds) dump the same positions."""
+    import numpy as np
+    import torch
+    import bench
+    big = (torch.arange(50_000, dtype=torch.int64) * 7) % 251
+    s1 = bench.dump_sample(torch, big, 1000, np.float32, 5)
+    s2 = bench.dump_sample(torch, big.clone(), 1000, np.float32, 5)
+    assert s1.dtype == np.float32 and s1.shape == (1000,) and np.array_equal(s1, s2)
+    idx = np.sort(np.random.default_rng(5).integers(0, 50_000, 1000, dtype=np.int64))
+    assert np.array_equal(s1, big.numpy()[idx].astype(np.float32))
+    assert np.array_equal(bench.dump_sample(torch, big, 50_000, np.float64, 5), big.numpy().astype(np.float64))
+    # three records of 2, 0 and 3 bytes in a larger output buffer
+    out = torch.tensor([9, 8, 7, 6, 5, 99, 99], dtype=torch.uint8)
+    rec = torch.tensor([0, 2, 2, 5], dtype=torch.int64)
+    err = torch.tensor([-1], dtype=torch.int64)
+    shapes = bench.dump_outputs(str(tmp_path / "d"), torch, 3, out, rec, err, 0, 1)
+    assert shapes == {"records": [5], "record_offsets": [4], "row_error": [1]}
+    got = {f: np.load(str(tmp_path / "d" / f)) for f in sorted(os.listdir(str(tmp_path / "d")))}
+    assert sorted(got) == ["record_offsets.npy", "records.npy", "row_error.npy"]
+    assert got["records.npy"].dtype == np.float32 and got["records.npy"].tolist() == [9, 8, 7, 6, 5]
+    assert got["record_offsets.npy"].dtype == np.float64 and got["record_offsets.npy"].tolist() == [0, 2, 2, 5]
+    assert got["row_error.npy"].dtype == np.float64 and got["row_error.npy"].tolist() == [-1]
+    assert sorted(bench.dump_outputs(str(tmp_path / "r"), torch, 3, out, rec, err, 1, 2)) == [
+        "record_offsets_rank1", "records_rank1", "row_error_rank1"]
+
+
 def test_rehearsal_line_carries_weak_and_strong():
     """profiles/r06/bench_n8_rehearsal.json: the driver's `python bench.py
     --gpus 8` path rehearsed on one GPU (8 gloo ranks on cuda:0,

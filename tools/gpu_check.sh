@@ -16,15 +16,15 @@ for s in $STEPS; do
   case $s in
     smoke) timeout -k 10 420 python -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1 || { echo "smoke failed rc=$?"; tail -30 "$O/smoke.log"; exit 1; } ;;
     tests) timeout -k 10 1000 python -u -m pytest tests -m gpu -x -v -p no:cacheprovider --timeout 400 --timeout-method thread --durations 15 > "$O/pytest_gpu.log" 2>&1 || { echo "tests failed rc=$?"; tail -40 "$O/pytest_gpu.log"; exit 1; } ;;
-    bench) timeout -k 10 600 python bench.py > "$O/bench.json" 2> "$O/bench.err" || { echo "bench failed rc=$?"; tail -30 "$O/bench.err"; exit 1; } ; cat "$O/bench.json" ;;
+    bench) timeout -k 10 600 python bench.py --full > "$O/bench.json" 2> "$O/bench.err" || { echo "bench failed rc=$?"; tail -30 "$O/bench.err"; exit 1; } ; cat "$O/bench.json" ;;
     bench0) timeout -k 10 600 python bench.py --law 0 --no-cpu-baseline > "$O/bench_law0.json" 2> "$O/bench_law0.err" || { echo "bench0 failed"; tail -30 "$O/bench_law0.err"; exit 1; } ; cat "$O/bench_law0.json" ;;
-    biobank) timeout -k 10 900 python bench.py --mode biobank --steps 5 --warmup 1 > "$O/bench_biobank.json" 2> "$O/bench_biobank.err" || { echo "biobank failed"; tail -30 "$O/bench_biobank.err"; exit 1; } ; cat "$O/bench_biobank.json" ;;
+    biobank) timeout -k 10 900 python bench.py --full --mode biobank --steps 5 --warmup 1 > "$O/bench_biobank.json" 2> "$O/bench_biobank.err" || { echo "biobank failed"; tail -30 "$O/bench_biobank.err"; exit 1; } ; cat "$O/bench_biobank.json" ;;
     profbio) (cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/profbio" -o run -- python3 "$R/bench.py" --mode biobank --steps 3 --warmup 1 --no-cpu-baseline > "$O/profbio.log" 2>&1) || { echo "profbio failed rc=$?"; tail -30 "$O/profbio.log"; exit 1; } ;;
     dtests) timeout -k 10 600 python -u -m pytest tests/test_gpu_dist_sparsify.py -x -v -p no:cacheprovider --timeout 300 --timeout-method thread > "$O/pytest_d.log" 2>&1 || { echo "dtests failed rc=$?"; tail -40 "$O/pytest_d.log"; exit 1; } ;;
     wtests) timeout -k 10 900 python -u -m pytest tests/test_gpu_encode.py -x -v -k synthetic -p no:cacheprovider --timeout 300 --timeout-method thread > "$O/pytest_w.log" 2>&1 || { echo "wtests failed rc=$?"; tail -40 "$O/pytest_w.log"; exit 1; } ;;
-    benchdec) timeout -k 10 600 python bench.py --mode decode > "$O/bench_decode.json" 2> "$O/bench_decode.err" || { echo "benchdec failed"; tail -30 "$O/bench_decode.err"; exit 1; } ; cat "$O/bench_decode.json" ;;
-    benchsp) timeout -k 10 900 python bench.py --mode sparse --steps 5 --warmup 1 > "$O/bench_sparse.json" 2> "$O/bench_sparse.err" || { echo "benchsp failed"; tail -30 "$O/bench_sparse.err"; exit 1; } ; cat "$O/bench_sparse.json" ;;
-    benchq) timeout -k 10 600 python bench.py --mode query > "$O/bench_query.json" 2> "$O/bench_query.err" || { echo "benchq failed"; tail -30 "$O/bench_query.err"; exit 1; } ; cat "$O/bench_query.json" ;;
+    benchdec) timeout -k 10 600 python bench.py --full --mode decode > "$O/bench_decode.json" 2> "$O/bench_decode.err" || { echo "benchdec failed"; tail -30 "$O/bench_decode.err"; exit 1; } ; cat "$O/bench_decode.json" ;;
+    benchsp) timeout -k 10 900 python bench.py --full --mode sparse --steps 5 --warmup 1 > "$O/bench_sparse.json" 2> "$O/bench_sparse.err" || { echo "benchsp failed"; tail -30 "$O/bench_sparse.err"; exit 1; } ; cat "$O/bench_sparse.json" ;;
+    benchq) timeout -k 10 600 python bench.py --full --mode query > "$O/bench_query.json" 2> "$O/bench_query.err" || { echo "benchq failed"; tail -30 "$O/bench_query.err"; exit 1; } ; cat "$O/bench_query.json" ;;
     profq) (cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/profq" -o run -- python3 "$R/bench.py" --mode query --steps 10 --warmup 2 --no-cpu-baseline > "$O/profq.log" 2>&1) || { echo "profq failed rc=$?"; tail -30 "$O/profq.log"; exit 1; } ;;
     pmcq) # HBM bytes per query step (k_query_match + selected decode) -> pmc_k_query.json
          for P in FETCH_SIZE WRITE_SIZE; do
@@ -32,7 +32,7 @@ for s in $STEPS; do
          done
          python3 tools/pmc_step_json.py "$O/pmcq_FETCH_SIZE" "$O/pmcq_WRITE_SIZE" 4 "chr22-shaped/2504x1000000/0.125" "$O/pmc_k_query.json" "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, bench.py --mode query --steps 3 --warmup 1 (tools/gpu_check.sh pmcq, run $TAG)" k_query_match "range query step (k_query_match + selected k_dec_plan / scan / k_dec_write)" > /dev/null || { echo "pmcq json failed"; exit 1; } ;;
     qtests) timeout -k 10 900 python -m pytest tests/test_gpu_query.py tests/test_gpu_decode.py -x -q -p no:cacheprovider > "$O/pytest_q.log" 2>&1 || { echo "qtests failed rc=$?"; tail -40 "$O/pytest_q.log"; exit 1; } ;;
-    benching) timeout -k 10 900 python bench.py --mode ingest --steps 3 --warmup 1 > "$O/bench_ingest.json" 2> "$O/bench_ingest.err" || { echo "benching failed"; tail -30 "$O/bench_ingest.err"; exit 1; } ; cat "$O/bench_ingest.json" ;;
+    benching) timeout -k 10 900 python bench.py --full --mode ingest --steps 3 --warmup 1 > "$O/bench_ingest.json" 2> "$O/bench_ingest.err" || { echo "benching failed"; tail -30 "$O/bench_ingest.err"; exit 1; } ; cat "$O/bench_ingest.json" ;;
     itests) timeout -k 10 900 python -m pytest tests/test_gpu_encode.py -x -q -p no:cacheprovider > "$O/pytest_i.log" 2>&1 || { echo "itests failed rc=$?"; tail -40 "$O/pytest_i.log"; exit 1; } ;;
     profdec) (cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/profdec" -o run -- python3 "$R/bench.py" --mode decode --steps 10 --warmup 2 --no-cpu-baseline > "$O/profdec.log" 2>&1) || { echo "profdec failed rc=$?"; tail -30 "$O/profdec.log"; exit 1; } ;;
     pmcdec) for P in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU" "FETCH_SIZE" "WRITE_SIZE" "GRBM_GUI_ACTIVE SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR"; do
@@ -50,7 +50,7 @@ for s in $STEPS; do
          done ;;
     distfile) timeout -k 10 600 python bench.py --mode distfile --steps 3 --warmup 1 > "$O/bench_distfile.json" 2> "$O/bench_distfile.err" || { echo "distfile failed"; tail -30 "$O/bench_distfile.err"; exit 1; } ; cat "$O/bench_distfile.json" ;;
     distfile2) VCFC_BENCH_REHEARSAL=1 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29621 bench.py --gpus 2 --mode distfile --steps 3 --warmup 1 --dist-dir /tmp/vcfc_distfile2 > "$O/bench_distfile2.json" 2> "$O/bench_distfile2.err" || { echo "distfile2 failed"; tail -30 "$O/bench_distfile2.err"; exit 1; } ; cat "$O/bench_distfile2.json" ;;
-    bench3) timeout -k 10 600 python bench.py --law 3 > "$O/bench_law3.json" 2> "$O/bench_law3.err" || { echo "bench3 failed"; tail -30 "$O/bench_law3.err"; exit 1; } ; cat "$O/bench_law3.json" ;;
+    bench3) timeout -k 10 600 python bench.py --full --law 3 > "$O/bench_law3.json" 2> "$O/bench_law3.err" || { echo "bench3 failed"; tail -30 "$O/bench_law3.err"; exit 1; } ; cat "$O/bench_law3.json" ;;
     pmcenc3) # encoder HBM bytes per launch for law 3 -> pmc_k_encode_law3.json
          for P in FETCH_SIZE WRITE_SIZE; do
            (cd /tmp && export TMPDIR=/tmp && timeout -s KILL 120 rocprofv3 --pmc $P --kernel-trace --output-format csv -d "$O/pmcenc_l3_$P" -o run -- python3 "$R/bench.py" --law 3 --steps 3 --warmup 1 --no-cpu-baseline > "$O/pmcenc_l3_$P.log" 2>&1) || { echo "pmcenc3 $P failed rc=$?"; tail -30 "$O/pmcenc_l3_$P.log"; exit 1; }
@@ -78,7 +78,7 @@ for s in $STEPS; do
     pmcinstall) # the PMC summaries this run just made become the ones bench.py reads (same-box lines)
          for f in "$O"/pmc_k_encode*.json "$O"/pmc_k_query.json "$O"/pmc_devfile_l*.json; do [ -f "$f" ] && cp "$f" profiles/; done; ls -l profiles/pmc_*.json ;;
     profbench) # the default bench command itself under rocprofv3: the JSON line and the kernel stats of one process
-         (cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/profbench" -o run -- python3 "$R/bench.py" > "$O/bench_under_prof.json" 2> "$O/profbench.log") || { echo "profbench failed rc=$?"; tail -30 "$O/profbench.log"; exit 1; } ; cat "$O/bench_under_prof.json" ;;
+         (cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/profbench" -o run -- python3 "$R/bench.py" --full > "$O/bench_under_prof.json" 2> "$O/profbench.log") || { echo "profbench failed rc=$?"; tail -30 "$O/profbench.log"; exit 1; } ; cat "$O/bench_under_prof.json" ;;
     benchdev) timeout -k 10 300 python bench.py --mode devfile > "$O/bench_devfile.json" 2> "$O/bench_devfile.err" || { echo "benchdev failed"; tail -30 "$O/bench_devfile.err"; exit 1; } ; cat "$O/bench_devfile.json" ;;
     pmcdev) # HBM bytes per devfile step (every kernel of one call), law ${LAW:-1} -> pmc_devfile_l<law>.json
          for P in FETCH_SIZE WRITE_SIZE; do
