@@ -76,6 +76,7 @@ int vcfc_ctx_set_line_index(vcfc_ctx *ctx, int mode);
 #define VCFC_TRACE_INGEST 1u        /* vcfc_compress_file/_buffer/_range: stage totals */
 #define VCFC_TRACE_DEVICE 2u        /* vcfc_compress_device: chunks, sample count, re-indexes */
 #define VCFC_TRACE_SPARSE_QUERY 4u  /* vcfc_sparse_query*: stage totals */
+#define VCFC_TRACE_INDEX 8u         /* vcfc_query_binned_index*: windows / bytes read by the indexed query */
 int vcfc_ctx_set_trace(vcfc_ctx *ctx, unsigned flags);
 /* Deferred records (1 = on, the default since round 5; 0 = off) for the
  * context's file and device compress calls (vcfc_encode_rows_device and the
@@ -286,6 +287,64 @@ int vcfc_query_file(vcfc_ctx *ctx, const char *in_vcfc, const char *ref, uint64_
 int vcfc_query_match_device(const uint8_t *d_in, const uint64_t *d_rec_start, uint64_t n, const uint8_t *d_ref,
                             uint64_t ref_len, int has_range, uint64_t start, uint64_t end, uint8_t *d_flag,
                             uint64_t *d_err, void *stream);
+
+/* ---- binned external index: create_binned_index4 (reference
+ * src/main.cpp:1284-1637, compute_end_position :763-852) and
+ * query_binned_index_binarysearch (:2974-3349; CLI :4097-4143) --------------
+ * The index of <file.vcfc> is <file.vcfc>.vcfci: packed 13-byte entries
+ * {u8 ref_idx, u32 position (LE), u64 byte_offset (LE)} (struct index_entry,
+ * :600-626).  ref_idx is 1..25 for CHROM "1".."22", "X", "Y", "M", else 0
+ * (reference_name_map, src/utils.hpp:97-100); a record's end position is POS
+ * + max(|REF|, longest ALT piece) - 1, or for an ALT holding '<' INFO's END,
+ * else POS + max |SVLEN| - 1, else POS.  Record 0 opens an entry; record i
+ * with i % entries_per_bin == 0 opens one iff its end passes the last
+ * entry's position; every other record only raises that position
+ * (:1436-1482).  byte_offset is the record's offset in the file (the
+ * reference's ftell, header bytes included).
+ *
+ * One deviation: a record whose first eight TABs do not all lie inside it
+ * (code 3) is refused with VCFC_E_FORMAT, where the reference reads on into
+ * the next record; no file written by compress has such a record. */
+#define VCFC_INDEX_ENTRY_BYTES 13
+uint64_t vcfc_index_workspace_size(uint64_t n_records);
+/* device-resident, async on stream: records d_in[d_rec_start[i], d_rec_start[i+1]),
+ * byte_offset of record i = base_offset + d_rec_start[i]; *d_count = entries;
+ * d_err as vcfc_query_match_device (codes 2, 3; 0xFF: entries_cap too small);
+ * d_info[0] = max end (caller replays on the host when > 0xFFFFFFFF: the
+ * reference then compares a 64-bit end with the entry's truncated u32
+ * position, :1442-1466, and the entries written here are not its) */
+int vcfc_binned_index_device(const uint8_t *d_in, const uint64_t *d_rec_start, uint64_t n, uint64_t base_offset,
+                             uint64_t entries_per_bin, uint8_t *d_entries, uint64_t entries_cap, uint64_t *d_count,
+                             uint64_t *d_info, void *d_ws, uint64_t ws_bytes, uint64_t *d_err, void *stream);
+/* per record: ref_idx, POS and the end position (compute_end_position,
+ * :763-852); d_err as above (codes 2, 3) */
+int vcfc_record_span_device(const uint8_t *d_in, const uint64_t *d_rec_start, uint64_t n, uint8_t *d_ref_idx,
+                            uint64_t *d_pos, uint64_t *d_end, uint64_t *d_err, void *stream);
+/* create_binned_index4 (:1284-1637) over .vcfc bytes / a file.
+ * entries_per_bin == 0: VCFC_E_ARG (the reference dies of SIGFPE).  Where
+ * the reference throws: VCFC_E_FORMAT, *err_record = the record, no index
+ * bytes (the reference writes its entries only at the end, :1621-1628; the
+ * file variant leaves <out_index> empty).  VCFC_E_NOSPACE: *out_len = bytes
+ * needed. */
+int vcfc_create_binned_index_buffer(vcfc_ctx *ctx, const uint8_t *in, uint64_t in_bytes, uint64_t entries_per_bin,
+                                    uint8_t *out, uint64_t out_cap, uint64_t *out_len, int64_t *err_record);
+int vcfc_create_binned_index_file(vcfc_ctx *ctx, const char *in_vcfc, const char *out_index,
+                                  uint64_t entries_per_bin);
+/* query_binned_index_binarysearch (:2974-3349): the binary search of
+ * :3047-3167 picks an entry, the walk of :3206-3329 starts at its
+ * byte_offset and outputs the lines of the records that compare_to_range
+ * (:110-137) places in (ref, start, end), up to the first record after it.
+ * A bare name (has_range == 0) queries start = end = 0 as the reference
+ * does.  An index whose size is not a multiple of 13: VCFC_E_FORMAT (the
+ * reference throws, :3018-3022); no entries: no output; one entry (the
+ * reference reads an uninitialised struct): entry 0.  Only the header and
+ * the bytes from that byte_offset on are read.  The _buffer variant returns
+ * VCFC_E_NOSPACE with *out_len = the size needed. */
+int vcfc_query_binned_index_buffer(vcfc_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const uint8_t *index,
+                                   uint64_t index_bytes, const char *ref, uint64_t ref_len, int has_range,
+                                   uint64_t start, uint64_t end, uint8_t *out, uint64_t out_cap, uint64_t *out_len);
+int vcfc_query_binned_index_file(vcfc_ctx *ctx, const char *in_vcfc, const char *in_index, const char *ref,
+                                 uint64_t ref_len, int has_range, uint64_t start, uint64_t end, int out_fd);
 
 /* ---- sparse layout: sparsify_file (reference src/sparse.cpp:290-580) -------
  * Record i of the .vcfc goes to data_start + (300e6 + POS_i) * 16384

@@ -1,9 +1,12 @@
 // main.cpp -- CLI with the reference's argv contract (src/main.cpp:4028-4185)
 // for the codec path: `main compress|decompress|sparsify <in> <out>` and
-// `main query|sparse-query <in> <query>`.  Data lines are
+// `main query|sparse-query <in> <query>`, and for the binned external index:
+// `main create-binned-index <bin-size> <in>` and
+// `main query-binned-index <in> <region>`.  Data lines are
 // encoded on the GPU through libvcfc.so.  Error messages mirror the
 // reference's exceptions (which terminate the reference process).
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <sys/stat.h>
@@ -12,7 +15,9 @@
 
 static int usage() {
     fprintf(stderr, "./main [compress|decompress|sparsify] <input_file> <output_file>\n"
-                    "./main [query|sparse-query] <input_file> <ref>[:<start>-<end>]\n");
+                    "./main [query|sparse-query] <input_file> <ref>[:<start>-<end>]\n"
+                    "./main create-binned-index <bin-size> <compressed-filename>\n"
+                    "./main query-binned-index <compressed-filename> <region>\n");
     return 1;
 }
 
@@ -152,6 +157,83 @@ int main(int argc, char **argv) {
         }
         if (st != VCFC_OK) {
             fprintf(stderr, "terminate called after throwing an instance of 'VcfValidationError'\n"
+                            "  what():  %s\n", vcfc_strerror(st));
+            return 134;
+        }
+        return 0;
+    }
+    if (action == "create-binned-index") {
+        // src/main.cpp:4097-4115 -> create_binned_index4 (:1284-1637): writes <file>.vcfci
+        if (argc != 4) {
+            printf("Usage: ./main create-binned-index <bin-size> <compressed-filename>\n");
+            return 1;
+        }
+        char *endp = nullptr;
+        const unsigned long bin = strtoul(argv[2], &endp, 10);   // str_to_uint64 (src/utils.cpp:152-165)
+        if (endp != argv[2] + strlen(argv[2]) || bin == 0) {     // (0: the reference dies of SIGFPE)
+            printf("bin size must be a positive integer\n");
+            return 1;
+        }
+        const std::string index = std::string(argv[3]) + ".vcfci";
+        if (!file_exists(argv[3])) {
+            perror("fopen");
+            fprintf(stderr, "terminate called after throwing an instance of 'std::runtime_error'\n"
+                            "  what():  Failed to open file: %s\n", argv[3]);
+            return 134;
+        }
+        vcfc_ctx *ctx = nullptr;
+        int st = vcfc_ctx_create(0, &ctx);
+        if (st != VCFC_OK) {
+            fprintf(stderr, "vcfc: %s\n", vcfc_strerror(st));
+            return 1;
+        }
+        st = vcfc_create_binned_index_file(ctx, argv[3], index.c_str(), bin);
+        vcfc_ctx_destroy(ctx);
+        if (st != VCFC_OK) {
+            fprintf(stderr, "terminate called after throwing an instance of 'std::runtime_error'\n"
+                            "  what():  %s\n", vcfc_strerror(st));
+            return 134;
+        }
+        return 0;
+    }
+    if (action == "query-binned-index") {
+        // src/main.cpp:4117-4143 -> query_binned_index_binarysearch (:2974-3349)
+        if (argc < 4) {
+            printf("Usage: ./main query-binned-index <compressed-filename> <region>");
+            return 1;
+        }
+        const std::string index = std::string(argv[2]) + ".vcfci";
+        if (!file_exists(argv[2])) {
+            printf("Input file does not exist: %s\n", argv[2]);
+            return 1;
+        }
+        if (!file_exists(index.c_str())) {
+            printf("Index file does not exist: %s\n", index.c_str());
+            return 1;
+        }
+        const std::string q(argv[3]);
+        uint64_t ref_len = 0, start = 0, end = 0;
+        int has_range = 0;
+        const int pq = vcfc_parse_query(q.data(), q.size(), &ref_len, &has_range, &start, &end);
+        if (pq != 0) {
+            const size_t colon = q.find(':'), dash = q.find('-', colon + 1);
+            if (pq == 1) printf("Query must contain a dash character: <ref>:<start>-<end>\n");
+            else if (pq == 2) printf("Failed to parse int from start position: %s\n", q.substr(colon + 1, dash - colon - 1).c_str());
+            else printf("Failed to parse int from end position: %s\n", q.substr(dash + 1).c_str());
+            printf("Failed to parse query string: %s\n", q.c_str());
+            return 1;
+        }
+        vcfc_ctx *ctx = nullptr;
+        int st = vcfc_ctx_create(0, &ctx);
+        if (st != VCFC_OK) {
+            fprintf(stderr, "vcfc: %s\n", vcfc_strerror(st));
+            return 1;
+        }
+        fflush(stdout);
+        st = vcfc_query_binned_index_file(ctx, argv[2], index.c_str(), q.data(), ref_len, has_range, start, end, 1);
+        vcfc_ctx_destroy(ctx);
+        if (st != VCFC_OK) {
+            fprintf(stderr, "terminate called after throwing an instance of 'std::runtime_error'\n"
                             "  what():  %s\n", vcfc_strerror(st));
             return 134;
         }

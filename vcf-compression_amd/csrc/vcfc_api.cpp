@@ -19,6 +19,7 @@
 #include "vcfc.h"
 #include "vcfc_decode_driver.h"
 #include "vcfc_device.h"
+#include "vcfc_index_driver.h"
 #include "vcfc_ingest_driver.h"
 
 hipError_t vcfc_sparse_plan_launch(const uint8_t *recs, const uint64_t *rec_off, uint64_t n, uint64_t data_start,
@@ -294,7 +295,7 @@ int vcfc_ctx_set_deferred_records(vcfc_ctx *c, int on) {
 }
 
 int vcfc_ctx_set_trace(vcfc_ctx *c, unsigned flags) {
-    if (!c || (flags & ~(VCFC_TRACE_INGEST | VCFC_TRACE_DEVICE | VCFC_TRACE_SPARSE_QUERY))) return VCFC_E_ARG;
+    if (!c || (flags & ~(VCFC_TRACE_INGEST | VCFC_TRACE_DEVICE | VCFC_TRACE_SPARSE_QUERY | VCFC_TRACE_INDEX))) return VCFC_E_ARG;
     c->trace = flags;
     return VCFC_OK;
 }
@@ -986,6 +987,151 @@ int vcfc_sparse_query_file(vcfc_ctx *c, const char *in_path, const char *ref, ui
     q.start = start; q.end = end;
     CtxDecodeBuffers B(c);
     const int st = vcfc_dec::sparse_query(fd, q, B, c->stream, sink, (c->trace & VCFC_TRACE_SPARSE_QUERY) != 0);
+    close(fd);
+    return st;
+}
+
+// ---- binned external index: create_binned_index4 (reference
+// src/main.cpp:1284-1637), query_binned_index_binarysearch (:2974-3349);
+// drivers in vcfc_index_driver.h ---------------------------------------------
+
+uint64_t vcfc_index_workspace_size(uint64_t n_records) { return vcfc_index_workspace_layout(n_records).total; }
+
+int vcfc_binned_index_device(const uint8_t *d_in, const uint64_t *d_rec_start, uint64_t n, uint64_t base_offset,
+                             uint64_t entries_per_bin, uint8_t *d_entries, uint64_t entries_cap, uint64_t *d_count,
+                             uint64_t *d_info, void *d_ws, uint64_t ws_bytes, uint64_t *d_err, void *stream) {
+    if ((n && (!d_in || !d_rec_start || !d_entries || !d_ws)) || !d_count || !d_info || !d_err || !entries_per_bin)
+        return VCFC_E_ARG;
+    const VcfcIndexLayout L = vcfc_index_workspace_layout(n);
+    if (n && ws_bytes < L.total) return VCFC_E_NOSPACE;
+    return vcfc_index_build(d_in, d_rec_start, n, base_offset, entries_per_bin, d_entries, entries_cap, d_count, d_info,
+                            static_cast<uint8_t *>(d_ws), L, d_err, static_cast<hipStream_t>(stream)) == hipSuccess
+               ? VCFC_OK : VCFC_E_HIP;
+}
+
+int vcfc_record_span_device(const uint8_t *d_in, const uint64_t *d_rec_start, uint64_t n, uint8_t *d_ref_idx,
+                            uint64_t *d_pos, uint64_t *d_end, uint64_t *d_err, void *stream) {
+    if ((n && (!d_in || !d_rec_start || !d_ref_idx || !d_pos || !d_end)) || !d_err) return VCFC_E_ARG;
+    return vcfc_index_span(d_in, d_rec_start, n, d_ref_idx, d_pos, d_end, d_err, static_cast<hipStream_t>(stream)) ==
+                   hipSuccess
+               ? VCFC_OK : VCFC_E_HIP;
+}
+
+int vcfc_create_binned_index_buffer(vcfc_ctx *c, const uint8_t *in, uint64_t n, uint64_t entries_per_bin, uint8_t *out,
+                                    uint64_t out_cap, uint64_t *out_len, int64_t *err_record) {
+    if (!c || (!in && n) || (!out && out_cap) || !out_len) return VCFC_E_ARG;
+    *out_len = 0;
+    if (err_record) *err_record = -1;
+    if (!entries_per_bin) return VCFC_E_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
+    CtxDecodeBuffers B(c);
+    std::vector<uint8_t> idx;
+    const int st = vcfc_idx::create_index(in, n, entries_per_bin, B, c->stream, idx, err_record);
+    if (st) return st;
+    *out_len = idx.size();
+    if (idx.size() > out_cap) return VCFC_E_NOSPACE;
+    if (!idx.empty()) memcpy(out, idx.data(), idx.size());
+    return VCFC_OK;
+}
+
+int vcfc_create_binned_index_file(vcfc_ctx *c, const char *in_path, const char *out_path, uint64_t entries_per_bin) {
+    if (!c || !in_path || !out_path || !entries_per_bin) return VCFC_E_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
+    MappedFile f;
+    int st = f.open_ro(in_path);
+    if (st) return st;
+    // the reference opens (truncates) the index before it reads the input and
+    // writes the entries only after the last record (:1293, :1621-1628)
+    const int fd = open(out_path, O_CREAT | O_TRUNC | O_WRONLY, 0644);
+    if (fd < 0) return VCFC_E_IO;
+    CtxDecodeBuffers B(c);
+    std::vector<uint8_t> idx;
+    st = vcfc_idx::create_index(f.p, f.n, entries_per_bin, B, c->stream, idx, nullptr);
+    if (!st && !idx.empty()) st = write_all_at(fd, idx.data(), idx.size(), 0);
+    if (close(fd) != 0 && !st) st = VCFC_E_IO;
+    return st;
+}
+
+namespace {
+struct MemReader : vcfc_idx::Reader {
+    const uint8_t *p;
+    uint64_t n;
+    MemReader(const uint8_t *b, uint64_t size) : p(b), n(size) {}
+    uint64_t size() const override { return n; }
+    int64_t read(uint8_t *dst, uint64_t off, uint64_t k) override {
+        if (off >= n) return 0;
+        k = std::min(k, n - off);
+        memcpy(dst, p + off, k);
+        return (int64_t)k;
+    }
+};
+struct FdReader : vcfc_idx::Reader {
+    int fd;
+    uint64_t n;
+    FdReader(int f, uint64_t size) : fd(f), n(size) {}
+    uint64_t size() const override { return n; }
+    int64_t read(uint8_t *dst, uint64_t off, uint64_t k) override { return vcfc_dec::sq_pread(fd, dst, k, off); }
+};
+void trace_index(const vcfc_ctx *c, const vcfc_idx::QueryStats &qs, uint64_t fsize) {
+    if (c->trace & VCFC_TRACE_INDEX)
+        fprintf(stderr, "query_binned_index: %llu windows, %llu bytes read of %llu, %llu records spanned\n",
+                (unsigned long long)qs.windows, (unsigned long long)qs.bytes, (unsigned long long)fsize,
+                (unsigned long long)qs.records);
+}
+}  // namespace
+
+int vcfc_query_binned_index_buffer(vcfc_ctx *c, const uint8_t *in, uint64_t n, const uint8_t *index,
+                                   uint64_t index_bytes, const char *ref, uint64_t ref_len, int has_range,
+                                   uint64_t start, uint64_t end, uint8_t *out, uint64_t out_cap, uint64_t *out_len) {
+    if (!c || (!in && n) || (!index && index_bytes) || (!ref && ref_len) || (!out && out_cap) || !out_len)
+        return VCFC_E_ARG;
+    *out_len = 0;
+    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
+    uint64_t o = 0;
+    bool fits = true;
+    auto sink = [&](const uint8_t *p, uint64_t k) {
+        if (fits && o + k <= out_cap) memcpy(out + o, p, k);
+        else fits = false;
+        o += k;
+        return true;
+    };
+    MemReader R(in, n);
+    CtxDecodeBuffers B(c);
+    vcfc_idx::QueryStats qs;
+    const int st = vcfc_idx::query_index(R, index, index_bytes, reinterpret_cast<const uint8_t *>(ref), ref_len,
+                                         has_range, start, end, B, c->stream, sink, 4ull << 20, &qs);
+    trace_index(c, qs, n);
+    *out_len = o;
+    if (!fits) return VCFC_E_NOSPACE;
+    return st;
+}
+
+int vcfc_query_binned_index_file(vcfc_ctx *c, const char *in_path, const char *index_path, const char *ref,
+                                 uint64_t ref_len, int has_range, uint64_t start, uint64_t end, int out_fd) {
+    if (!c || !in_path || !index_path || (!ref && ref_len) || out_fd < 0) return VCFC_E_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
+    MappedFile idx;   // the index is small: read whole
+    int st = idx.open_ro(index_path);
+    if (st) return st;
+    const int fd = open(in_path, O_RDONLY);
+    if (fd < 0) return VCFC_E_IO;
+    struct stat sb;
+    if (fstat(fd, &sb) != 0) { close(fd); return VCFC_E_IO; }
+    auto sink = [&](const uint8_t *p, uint64_t k) {
+        while (k) {
+            const ssize_t w = write(out_fd, p, std::min<uint64_t>(k, 1ull << 30));
+            if (w <= 0) return false;
+            p += w;
+            k -= (uint64_t)w;
+        }
+        return true;
+    };
+    FdReader R(fd, (uint64_t)sb.st_size);
+    CtxDecodeBuffers B(c);
+    vcfc_idx::QueryStats qs;
+    st = vcfc_idx::query_index(R, idx.p, idx.n, reinterpret_cast<const uint8_t *>(ref), ref_len, has_range, start, end,
+                               B, c->stream, sink, 4ull << 20, &qs);
+    trace_index(c, qs, (uint64_t)sb.st_size);
     close(fd);
     return st;
 }

@@ -293,3 +293,31 @@ hipError_t vcfc_line_index_place(const uint8_t *buf, uint64_t n, uint64_t n_line
                                  const VcfcLineIndexLayout &L, const VcfcLineIndex &x, hipStream_t s);
 // counts[0..3] and the first pk '#' line entries into out (32 + 24 pk bytes)
 hipError_t vcfc_index_summary(const VcfcLineIndex &x, uint64_t pk, uint8_t *out, hipStream_t s);
+
+// ---------------------------------------------------------------------------
+// Binned external index (vcfc_index.hip; reference create_binned_index4,
+// src/main.cpp:1284-1637, and query_binned_index_binarysearch, :2974-3349).
+struct VcfcIndexLayout {
+    uint64_t ref_idx, pos, end, pmax, flag, eno, bmax, partials, total;
+};
+VcfcIndexLayout vcfc_index_workspace_layout(uint64_t n);
+// one lane per record [rec_start[i], rec_start[i + 1]): ref_idx (1..25 for
+// "1".."22", "X", "Y", "M", else 0), POS and the end position
+// (compute_end_position, :763-852); err = min over records of (i << 8 |
+// code), code 2 = the reference throws (POS, an INFO pair, END or SVLEN does
+// not parse), 3 = the first eight TABs do not all lie inside the record
+hipError_t vcfc_index_span(const uint8_t *in, const uint64_t *rec_start, uint64_t n, uint8_t *ref_idx, uint64_t *pos,
+                           uint64_t *end, uint64_t *err, hipStream_t s);
+// span + prefix maximum + open flags + entry numbers + the packed 13-byte
+// entries {u8 ref_idx, u32 position, u64 base_offset + rec_start[k]};
+// *count = entries, *info = the largest end (the entries hold the
+// reference's only while it is below 2^32); err as vcfc_index_span, and
+// code 0xFF: an entry past entries_cap.  No host synchronisation.
+hipError_t vcfc_index_build(const uint8_t *in, const uint64_t *rec_start, uint64_t n, uint64_t base_offset,
+                            uint64_t entries_per_bin, uint8_t *entries, uint64_t entries_cap, uint64_t *count,
+                            uint64_t *info, uint8_t *ws, const VcfcIndexLayout &L, uint64_t *err, hipStream_t s);
+// compare_to_range (:110-137) per record: flag[i] = 1 where the record lies
+// in the query; *first_after = the first record after it (~0: none)
+hipError_t vcfc_index_compare(const uint8_t *ref_idx, const uint64_t *pos, const uint64_t *end, uint64_t n,
+                              uint32_t qidx, uint64_t qstart, uint64_t qend, uint8_t *flag, uint64_t *first_after,
+                              hipStream_t s);

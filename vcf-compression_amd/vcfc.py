@@ -5,6 +5,7 @@ Mirrors the reference's operator interface for the encode path:
   compress_file(in_path, out_path)             (reference src/compress.cpp:205-257)
   decompress / decompress_file                 (reference src/compress.cpp:1214-1257)
   parse_coordinate_string, query / query_file  (reference src/main.cpp:3777-4026)
+  create_binned_index / query_binned_index     (reference src/main.cpp:1284-1637, 2974-3349)
 Errors raise VcfValidationError / RuntimeError like the reference's exceptions
 (src/utils.hpp:117-123, src/compress.cpp:9-11,231-234).
 
@@ -41,9 +42,14 @@ EXPORTS = [
     "vcfc_compress_range", "vcfc_compress_device", "vcfc_compress_range_held", "vcfc_held_place",
     "vcfc_held_sizes", "vcfc_held_free", "vcfc_ctx_set_line_index", "vcfc_ctx_set_trace",
     "vcfc_ctx_set_deferred_records", "vcfc_encode_deferred_rows",
+    "vcfc_index_workspace_size", "vcfc_binned_index_device", "vcfc_record_span_device",
+    "vcfc_create_binned_index_buffer", "vcfc_create_binned_index_file",
+    "vcfc_query_binned_index_buffer", "vcfc_query_binned_index_file",
 ]
 LINE_INDEX_HOP, LINE_INDEX_SCAN = 0, 1                       # include/vcfc.h VCFC_LINE_INDEX_*
 TRACE_INGEST, TRACE_DEVICE, TRACE_SPARSE_QUERY = 1, 2, 4     # include/vcfc.h VCFC_TRACE_*
+TRACE_INDEX = 8
+INDEX_ENTRY_BYTES = 13                                       # include/vcfc.h VCFC_INDEX_ENTRY_BYTES
 
 
 class VcfValidationError(RuntimeError):
@@ -78,10 +84,22 @@ def lib():
     # that the current build exports every one of them.
     late = {"vcfc_ctx_set_line_index": [vp, ctypes.c_int], "vcfc_ctx_set_trace": [vp, ctypes.c_uint],
             "vcfc_ctx_set_deferred_records": [vp, ctypes.c_int],
-            "vcfc_encode_deferred_rows": [vp, u64, u64, vp, ctypes.POINTER(u64)]}
+            "vcfc_encode_deferred_rows": [vp, u64, u64, vp, ctypes.POINTER(u64)],
+            # the binned external index
+            "vcfc_index_workspace_size": [u64],
+            "vcfc_binned_index_device": [vp, vp, u64, u64, u64, vp, u64, vp, vp, vp, u64, vp, vp],
+            "vcfc_record_span_device": [vp, vp, u64, vp, vp, vp, vp, vp],
+            "vcfc_create_binned_index_buffer": [vp, vp, u64, u64, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(i64)],
+            "vcfc_create_binned_index_file": [vp, ctypes.c_char_p, ctypes.c_char_p, u64],
+            "vcfc_query_binned_index_buffer": [vp, vp, u64, vp, u64, ctypes.c_char_p, u64, ctypes.c_int, u64, u64, vp,
+                                               u64, ctypes.POINTER(u64)],
+            "vcfc_query_binned_index_file": [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, u64, ctypes.c_int,
+                                             u64, u64, ctypes.c_int]}
     for name, args in late.items():
         if hasattr(L, name):
             getattr(L, name).argtypes = args
+    if hasattr(L, "vcfc_index_workspace_size"):
+        L.vcfc_index_workspace_size.restype = u64
     L.vcfc_record_hash_device.argtypes = [vp, vp, u64, vp, vp]
     L.vcfc_compress_range.argtypes = [vp, ctypes.c_char_p, u64, u64, ctypes.c_int, u64, ctypes.POINTER(u64),
                                       ctypes.POINTER(i64), ctypes.POINTER(u64)]
@@ -444,6 +462,74 @@ class Context:
                                                len(query.reference_name), int(query.has_range), query.start,
                                                query.end, out_fd))
 
+    # -- binned external index (reference src/main.cpp:1284-1637, 2974-3349) --
+    def create_binned_index_status(self, data, entries_per_bin):
+        """create_binned_index4 over .vcfc bytes: (status, index bytes,
+        err_record).  E_FORMAT where the reference throws (no bytes;
+        err_record = the record), E_ARG for entries_per_bin == 0."""
+        src = np.frombuffer(data, dtype=np.uint8)
+        cap = 4096
+        while True:
+            out = np.empty(cap, dtype=np.uint8)
+            n, er = ctypes.c_uint64(0), ctypes.c_int64(-1)
+            st = _need("vcfc_create_binned_index_buffer")(self._h, src.ctypes.data, len(data), int(entries_per_bin),
+                                                          out.ctypes.data, cap, ctypes.byref(n), ctypes.byref(er))
+            if st == E_NOSPACE and n.value > cap:
+                cap = n.value
+                continue
+            return st, out[:n.value].tobytes() if st == OK else b"", er.value
+
+    def create_binned_index(self, data, entries_per_bin):
+        """The bytes of <file>.vcfci for .vcfc bytes `data` (13-byte entries),
+        raising where the reference throws."""
+        st, out, er = self.create_binned_index_status(data, entries_per_bin)
+        raise_for(st, "record %d" % er if er >= 0 else "")
+        return out
+
+    def create_binned_index_file(self, in_path, entries_per_bin, index_path=None):
+        """`main create-binned-index <bin> <in_path>`: writes in_path + ".vcfci"
+        (or index_path)."""
+        index_path = index_path or in_path + ".vcfci"
+        raise_for(_need("vcfc_create_binned_index_file")(self._h, in_path.encode(), index_path.encode(),
+                                                         int(entries_per_bin)))
+
+    def query_binned_index_status(self, data, index, query, cap=None):
+        """query_binned_index_binarysearch over .vcfc bytes and their index
+        bytes: (status, lines).  On E_FORMAT the bytes are every line written
+        before the reference throws."""
+        if not isinstance(query, VcfCoordinateQuery):
+            query = parse_coordinate_string(query)
+        src = np.frombuffer(data, dtype=np.uint8)
+        idx = np.frombuffer(index, dtype=np.uint8)
+        cap = cap if cap is not None else 1 << 20
+        while True:
+            out = np.empty(max(cap, 1), dtype=np.uint8)
+            n = ctypes.c_uint64(0)
+            st = _need("vcfc_query_binned_index_buffer")(self._h, src.ctypes.data, len(data),
+                                                         idx.ctypes.data if len(index) else None, len(index),
+                                                         query.reference_name, len(query.reference_name),
+                                                         int(query.has_range), query.start, query.end,
+                                                         out.ctypes.data, cap, ctypes.byref(n))
+            if st == E_NOSPACE and n.value > cap:
+                cap = n.value
+                continue
+            return st, out[:n.value].tobytes()
+
+    def query_binned_index(self, data, index, query):
+        """Like query_binned_index_status, raising where the reference throws."""
+        st, out = self.query_binned_index_status(data, index, query)
+        raise_for(st)
+        return out
+
+    def query_binned_index_file(self, in_path, query, out_fd=1, index_path=None):
+        """`main query-binned-index <in_path> <region>`: lines to out_fd."""
+        if not isinstance(query, VcfCoordinateQuery):
+            query = parse_coordinate_string(query)
+        index_path = index_path or in_path + ".vcfci"
+        raise_for(_need("vcfc_query_binned_index_file")(self._h, in_path.encode(), index_path.encode(),
+                                                        query.reference_name, len(query.reference_name),
+                                                        int(query.has_range), query.start, query.end, out_fd))
+
     def sparsify_file(self, in_path, out_path):
         """sparsify_file (reference src/sparse.cpp:290-580)."""
         raise_for(lib().vcfc_sparsify_file(self._h, in_path.encode(), out_path.encode()))
@@ -568,3 +654,20 @@ def synth_rows_device(d_buf, d_line_off, n, d_prefix, d_prefix_off, d_row_af, sa
 def record_hash_device(d_recs, d_rec_off, n, d_hash, stream=0):
     """Per-record 64-bit digests on the GPU (include/vcfc.h vcfc_record_hash_device)."""
     raise_for(lib().vcfc_record_hash_device(d_recs, d_rec_off, n, d_hash, stream))
+
+
+def index_workspace_size(n_records):
+    return int(_need("vcfc_index_workspace_size")(n_records))
+
+
+def binned_index_device(d_in, d_rec_start, n, base_offset, entries_per_bin, d_entries, entries_cap, d_count, d_info,
+                        d_ws, ws_bytes, d_err, stream=0):
+    """The packed index entries of device-resident records (include/vcfc.h
+    vcfc_binned_index_device); enqueued on `stream`."""
+    raise_for(_need("vcfc_binned_index_device")(d_in, d_rec_start, n, base_offset, entries_per_bin, d_entries,
+                                                entries_cap, d_count, d_info, d_ws, ws_bytes, d_err, stream))
+
+
+def record_span_device(d_in, d_rec_start, n, d_ref_idx, d_pos, d_end, d_err, stream=0):
+    """Per record ref_idx (u8), POS and end position (u64 each) on the GPU."""
+    raise_for(_need("vcfc_record_span_device")(d_in, d_rec_start, n, d_ref_idx, d_pos, d_end, d_err, stream))
