@@ -346,6 +346,89 @@ int vcfc_query_binned_index_buffer(vcfc_ctx *ctx, const uint8_t *in, uint64_t in
 int vcfc_query_binned_index_file(vcfc_ctx *ctx, const char *in_vcfc, const char *in_index, const char *ref,
                                  uint64_t ref_len, int has_range, uint64_t start, uint64_t end, int out_fd);
 
+/* ---- sparse external index: create_sparse_external_index (reference
+ * src/main.cpp:854-999; CLI :4144-4157) and query_sparse_external_index
+ * (:1002-1281; CLI :4158-4177) ----------------------------------------------
+ * The index of <file.vcfc> is <file.vcfc>.vcfci-sparse, a sparse file: the
+ * entry of a record {u8 ref_idx, u32 (uint32)POS (LE), u64 byte_offset (LE)}
+ * (the binned index's 13 packed bytes) lies at file offset (300000000 + POS)
+ * * 256 in 64-bit wrap-around arithmetic (compute_sparse_offset,
+ * src/sparse.cpp:18-51, with multiplication_factor 1 and block size 256;
+ * CHROM is not part of it, VCFC_SPARSE_MULTIPLE_REF_PER_FILE being false).
+ * The reference writes one entry per record in file order, so of the records
+ * that share a slot the last one stays.  CHROM .. ALT are the bytes up to the
+ * first five TABs; QUAL, FILTER and INFO are read only when ALT holds '<',
+ * and compute_end_position (:763-852) then runs for its throws alone.
+ *
+ * One deviation: a record whose five (eight for a structural ALT) TABs do
+ * not all lie inside it (code 3) is refused with VCFC_E_FORMAT, where the
+ * reference reads on into the next record; no file written by compress has
+ * such a record. */
+uint64_t vcfc_sparse_index_workspace_size(uint64_t n_records);
+/* compute_sparse_offset (src/sparse.cpp:18-51) for the index: the file
+ * offset of the slot of `pos` */
+uint64_t vcfc_sparse_index_offset(uint64_t pos);
+/* device-resident, async on stream: records d_in[d_rec_start[i],
+ * d_rec_start[i+1]), byte_offset of record i = base_offset + d_rec_start[i].
+ * Of each run of records with equal slot offsets the last is kept; the kept
+ * entries (13 bytes each) and their file offsets are written densely, in
+ * record order, to d_entries (13 n bytes) and d_file_off (n words); *d_count
+ * = kept entries.  d_status (3 words): [1] = 1 where some record's offset is
+ * below its predecessor's -- the kept set is then not what the reference's
+ * sequential writes leave, and the caller writes every record in order;
+ * [2] = the first record whose offset is negative as off_t (the reference's
+ * lseek fails there, :954-959), ~0 for none; [0] = 0.  d_err as
+ * vcfc_binned_index_device (codes 2, 3). */
+int vcfc_sparse_index_device(const uint8_t *d_in, const uint64_t *d_rec_start, uint64_t n, uint64_t base_offset,
+                             uint8_t *d_entries, uint64_t *d_file_off, uint64_t *d_count, uint64_t *d_status,
+                             void *d_ws, uint64_t ws_bytes, uint64_t *d_err, void *stream);
+/* create_sparse_external_index (:854-999): <out_index> is opened O_CREAT |
+ * O_TRUNC, mode 0600, before the input is parsed.  The run stops at the
+ * first record the reference throws on (VCFC_E_FORMAT, *err_record = the
+ * record; also for a record header it cannot read) or cannot seek to
+ * (VCFC_OK, *seek_failed = 1: the reference prints "lseek: Invalid argument"
+ * and exits 0); the entries of the records before it are in the file either
+ * way.  A header without a data line: VCFC_E_FORMAT, *err_record = -1, the
+ * index left empty.  err_record and seek_failed may be null. */
+int vcfc_create_sparse_index_file(vcfc_ctx *ctx, const char *in_vcfc, const char *out_index, int64_t *err_record,
+                                  int *seek_failed);
+/* query_sparse_external_index (:1002-1281).  Lookup (:1040-1174): the
+ * SEEK_DATA probe at offset 10000000 must find data (an index without an
+ * entry: no output); the entry at the slot of `start` (a bare name,
+ * has_range == 0, queries start = end = 0; CHROM is ignored); at or past
+ * EOF: no output; an all-zero entry: no output when start == end, else the
+ * first non-zero slot after it (SEEK_DATA, then steps of 256).  Walk
+ * (:1191-1266): from the entry's byte_offset, records for which compare_to
+ * (:88-108) places (CHROM, POS) before the query are skipped -- and, unlike
+ * the reference, not decoded --, those inside it are output, the first one
+ * after it ends the walk.  A POS that does not parse: VCFC_E_FORMAT after the
+ * lines before it.  Only the header and the bytes from that byte_offset on
+ * are read. */
+int vcfc_query_sparse_index_file(vcfc_ctx *ctx, const char *in_vcfc, const char *in_index, const char *ref,
+                                 uint64_t ref_len, int has_range, uint64_t start, uint64_t end, int out_fd);
+
+/* ---- gap-analysis: gap_analysis (reference src/main.cpp:3931-3980) ---------
+ * Line sizes without the lines: the decoder's exact plan (the sizing pass of
+ * decompress2_data_line, src/compress.cpp:741-986) without its write pass.
+ * d_line_off: n + 1 exclusive offsets of the decoded lines (LF included);
+ * d_pos_off / d_pos_len: where each line's POS text (its second non-empty
+ * TAB field) lies in d_in; d_ccount: the reference's compressed count
+ * (line_byte_count, src/compress.cpp:764-968): the 8 header bytes, the
+ * required columns and each sample-section byte read, the closing LF counted
+ * only where it ends an uncompressed column.  The last three may all be
+ * null.  d_err: ~0 or (i << 8 | code) of the first record the decoder
+ * refuses (its codes 2, 3); entries from record i on are undefined. */
+uint64_t vcfc_decode_sizes_workspace_size(uint64_t n_records);
+int vcfc_decode_sizes_device(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_rec_start, uint64_t n,
+                             uint64_t sample_count, uint64_t *d_line_off, uint64_t *d_pos_off, uint32_t *d_pos_len,
+                             uint64_t *d_ccount, void *d_ws, uint64_t ws_bytes, uint64_t *d_err, void *stream);
+/* gap_analysis (:3931-3980): writes <out_txt> (truncated first; the CLI
+ * passes "start-positions.txt"), one line "<POS> <decoded line bytes>
+ * <compressed count>\n" per record, POS verbatim.  Where the reference throws
+ * (a header without a data line, a record the decoder refuses):
+ * VCFC_E_FORMAT, the lines of the records before it written. */
+int vcfc_gap_analysis_file(vcfc_ctx *ctx, const char *in_vcfc, const char *out_txt);
+
 /* ---- sparse layout: sparsify_file (reference src/sparse.cpp:290-580) -------
  * Record i of the .vcfc goes to data_start + (300e6 + POS_i) * 16384
  * (compute_sparse_offset, src/sparse.cpp:18-51) behind a 16-byte prefix

@@ -1,0 +1,295 @@
+"""GPU parity for the sparse external index (reference
+create_sparse_external_index, src/main.cpp:854-999, and
+query_sparse_external_index, :1002-1281) and gap-analysis (:3931-3980):
+against the reference CLI's recorded index contents, stdout, stderr and exit
+codes (tests/golden/sparse_index_cases.json) through the C ABI (libvcfc.so)
+and the CLI (build/main), the device entry points on freshly encoded batches
+against the restatement (sparse_index_cases.py), and one 2504-sample file
+against the VCF's own lines.  Malformed files beyond the golden ones run on
+the emulator (test_sparse_index_emu.py)."""
+import io
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+import pytest
+
+import golden_io as G
+import index_cases as X
+import sparse_index_cases as SX
+
+pytestmark = pytest.mark.gpu
+REPO = G.REPO
+sys.path.insert(0, os.path.join(REPO, "vcf-compression_amd"))
+MAIN = os.path.join(REPO, "build", "main")
+OK, E_FORMAT = 0, 8
+NO_ERROR = (1 << 64) - 1
+FILES = [c["file"] for c in SX.cases()["create_cases"]]
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    import torch   # before libvcfc: one HIP runtime in the process
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    import vcfc
+    c = vcfc.Context(0)
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def wd():
+    with tempfile.TemporaryDirectory() as d:
+        yield d
+
+
+def put(wd, name):
+    path = os.path.join(wd, name.replace(".", "_") + ".vcfc")
+    if not os.path.exists(path):
+        with open(path, "wb") as f:
+            f.write(SX.file_bytes(name))
+    return path
+
+
+def query_abi(ctx, path, region, wd):
+    out = os.path.join(wd, "q.out")
+    fd = os.open(out, os.O_CREAT | os.O_TRUNC | os.O_WRONLY, 0o600)
+    try:
+        try:
+            ctx.query_sparse_index(path, region, out_fd=fd)
+            st = OK
+        except RuntimeError:
+            st = E_FORMAT
+    finally:
+        os.close(fd)
+    with open(out, "rb") as f:
+        return st, f.read()
+
+
+@pytest.mark.parametrize("name", FILES)
+def test_abi_golden_cases(ctx, wd, name):
+    """create, every query and gap-analysis of one golden file through the C ABI."""
+    c = SX.create_case(name)
+    path = put(wd, name)
+    st, bad, sf = ctx.create_sparse_index_status(path)
+    slots, size = SX.read_sparse_file(path + ".vcfci-sparse")
+    assert os.stat(path + ".vcfci-sparse").st_mode & 0o777 == 0o600
+    assert SX.check_create_case(c, slots, size), (name, len(slots), size)
+    want = SX.create(SX.file_bytes(name))
+    assert (st, bad, sf) == (want[0], want[2], want[3]) and (st == OK) == (c["rc"] == 0)
+    assert sf == (1 if c.get("stderr") == "lseek: Invalid argument\n" else 0)
+    n = 0
+    for q in SX.cases()["query_cases"]:
+        if q["file"] != name:
+            continue
+        st, out = query_abi(ctx, path, q["region"], wd)
+        assert X.check_query_case(q, st, out), (q, st, len(out))
+        assert (st, out) == SX.query(SX.file_bytes(name), slots, q["region"])
+        n += 1
+    assert n >= 2
+    g = [g for g in SX.cases()["gap_cases"] if g["file"] == name][0]
+    txt_path = os.path.join(wd, "gap.txt")
+    if os.path.exists(txt_path):
+        os.unlink(txt_path)
+    try:
+        ctx.gap_analysis(path, txt_path)
+        st = OK
+    except RuntimeError:
+        st = E_FORMAT
+    txt = open(txt_path, "rb").read() if os.path.exists(txt_path) else b""
+    assert (st == OK) == (g["rc"] == 0) and len(txt) == g["txt_len"] and X.sha(txt) == g["txt_sha256"], name
+    if g["rc"] != 0:
+        assert not os.path.exists(txt_path)   # thrown before the output is opened
+
+
+@pytest.mark.parametrize("name", FILES)
+def test_cli_golden_cases(name):
+    """create-sparse-index, every query-sparse-index and gap-analysis of one
+    golden file through build/main: index contents, stdout, exit codes, and
+    stderr where the reference exits 0."""
+    c = SX.create_case(name)
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "f.vcfc")
+        with open(path, "wb") as f:
+            f.write(SX.file_bytes(name))
+        r = subprocess.run([MAIN, "create-sparse-index", path], capture_output=True, timeout=300)
+        slots, size = SX.read_sparse_file(path + ".vcfci-sparse")
+        assert SX.check_create_case(c, slots, size), (name, len(slots), size, r.stderr)
+        assert r.stdout == b"" and r.returncode == (0 if c["rc"] == 0 else 134), (r.returncode, r.stderr)
+        if c["rc"] == 0:
+            assert r.stderr.decode() == c["stderr"]
+        for q in SX.cases()["query_cases"]:
+            if q["file"] != name:
+                continue
+            r = subprocess.run([MAIN, "query-sparse-index", path, q["region"]], capture_output=True, timeout=300)
+            if q["rc"] == 0:
+                assert r.returncode == 0 and len(r.stdout) == q["stdout_len"], (q, r.stderr)
+                assert X.sha(r.stdout) == q["stdout_sha256"] and r.stderr.decode() == q["stderr"], (q, r.stderr)
+            else:   # reference: SIGABRT after a partial flush; here exit 134 after every line before the throw
+                assert r.returncode == 134, (q, r.stderr)
+                assert r.stdout == SX.query(SX.file_bytes(name), slots, q["region"])[1]
+                assert X.sha(r.stdout[:q["stdout_len"]]) == q["stdout_sha256"], q
+        g = [g for g in SX.cases()["gap_cases"] if g["file"] == name][0]
+        r = subprocess.run([MAIN, "gap-analysis", path], capture_output=True, timeout=300, cwd=d)
+        sp = os.path.join(d, "start-positions.txt")
+        txt = open(sp, "rb").read() if os.path.exists(sp) else b""
+        assert r.returncode == (0 if g["rc"] == 0 else 134) and r.stdout == b"", (r.returncode, r.stderr)
+        assert len(txt) == g["txt_len"] and X.sha(txt) == g["txt_sha256"]
+        assert "txt" not in g or txt.decode() == g["txt"]
+
+
+def test_cli_messages():
+    with tempfile.TemporaryDirectory() as wd:
+        f, n = os.path.join(wd, "f.vcfc"), os.path.join(wd, "noidx.vcfc")
+        for p in (f, n):
+            with open(p, "wb") as fh:
+                fh.write(SX.file_bytes("index_edge"))
+        SX.write_sparse_file(f + ".vcfci-sparse", SX.create(SX.file_bytes("index_edge"))[1])
+        sub = {"{f}": f, "{m}": os.path.join(wd, "missing.vcfc"), "{n}": n}
+        for c in SX.cases()["cli_cases"]:
+            r = subprocess.run([MAIN] + [sub.get(a, a) for a in c["argv"]], capture_output=True, timeout=300, cwd=wd)
+            out, err = r.stdout.decode(), r.stderr.decode()
+            for k, v in sub.items():
+                out, err = out.replace(v, k), err.replace(v, k)
+            assert (r.returncode, out) == (c["rc"] if c["rc"] >= 0 else 134, c["stdout"]), (c, r.stderr)
+            if c["rc"] == 0:
+                assert err == c["stderr"], c
+        assert not os.path.exists(sub["{m}"] + ".vcfci-sparse")   # thrown before the index is created
+        # the documented deviation: no file name (the reference dies in std::string(nullptr))
+        r = subprocess.run([MAIN, "gap-analysis"], capture_output=True, timeout=300, cwd=wd)
+        assert r.returncode == 1 and r.stdout == b"" and b"gap-analysis <compressed-filename>" in r.stderr
+        assert b"create-sparse-index" in r.stderr and b"query-sparse-index" in r.stderr
+
+
+PAIRS = {1: (), 2: (0,), 63: (5,), 64: (62,), 65: (63,), 255: (63, 100), 256: (63, 254), 257: (63, 255),
+         4097: (63, 255, 256, 4095), 70001: (63, 255, 4095, 65535, 69999)}
+
+
+def encode_on_gpu(lines, samples):
+    """Encode data lines on the GPU: (d_out, d_rec_off, host record offsets, the .vcfc bytes)."""
+    import torch
+    import vcfc
+    dev = "cuda:0"
+    n = len(lines)
+    ll = np.array([len(x) for x in lines], dtype=np.uint32)
+    lo = np.zeros(n, dtype=np.uint64)
+    lo[1:] = np.cumsum(ll[:-1].astype(np.uint64) + 1)
+    buf = np.frombuffer(b"\n".join(lines) + b"\n", dtype=np.uint8)
+    total = int(ll.sum(dtype=np.uint64))
+    t_buf = torch.from_numpy(buf.copy()).to(dev)
+    t_lo = torch.from_numpy(lo.view(np.int64)).to(dev)
+    t_ll = torch.from_numpy(ll.view(np.int32)).to(dev)
+    cap = vcfc.encode_bound(n, total)
+    wsb = vcfc.workspace_size(n, total)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    rec = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    err = torch.empty(1, dtype=torch.int64, device=dev)
+    s = torch.cuda.current_stream().cuda_stream
+    vcfc.encode_rows_device(t_buf.data_ptr(), t_lo.data_ptr(), t_ll.data_ptr(), n, total, out.data_ptr(), cap,
+                            rec.data_ptr(), ws.data_ptr(), wsb, err.data_ptr(), s)
+    torch.cuda.synchronize()
+    assert int(err.item()) == -1
+    r = rec.cpu().numpy()
+    v = X.header(samples) + out[:int(r[n])].cpu().numpy().tobytes()
+    return out, rec, r, v
+
+
+@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 255, 256, 257, 4097, 70001])
+def test_device_entry_points(n):
+    """Encode S = 2 rows on the GPU, then index the encoder's d_out /
+    d_rec_off in place: kept entries, offsets, count and status against the
+    restatement; then the sizes-only decode against the restatement's
+    gap-analysis."""
+    import torch
+    import vcfc
+    dev = "cuda:0"
+    lines = [b"\t".join([f[0], b"%d" % (50 + 3 * (i - sum(1 for p in PAIRS[n] if p < i)))] + f[2:])
+             for i, f in enumerate(x.split(b"\t") for x in X.gen_lines(n, 2000 + n, samples=2))]
+    out, rec, r, v = encode_on_gpu(lines, 2)
+    hdr = len(X.header(2))
+    s = torch.cuda.current_stream().cuda_stream
+    err = torch.empty(1, dtype=torch.int64, device=dev)
+    wsb = vcfc.sparse_index_workspace_size(n)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    ent = torch.full((13 * n + 16,), 0xEE, dtype=torch.uint8, device=dev)
+    fo = torch.full((n + 2,), -1, dtype=torch.int64, device=dev)
+    words = torch.empty(4, dtype=torch.int64, device=dev)   # count, status[0..2]
+    vcfc.sparse_index_device(out.data_ptr(), rec.data_ptr(), n, hdr, ent.data_ptr(), fo.data_ptr(), words.data_ptr(),
+                             words.data_ptr() + 8, ws.data_ptr(), wsb, err.data_ptr(), s)
+    torch.cuda.synchronize()
+    assert int(err.item()) == -1
+    w = [int(x) for x in words.cpu().numpy().view(np.uint64)]
+    want = SX.create(v)
+    assert want[0] == OK and len(want[1]) == n - len(PAIRS[n])
+    assert w == [len(want[1]), 0, 0, NO_ERROR], (n, w)
+    offs = sorted(want[1])
+    got_e, got_o = ent.cpu().numpy(), fo.cpu().numpy().view(np.uint64)
+    assert got_o[:len(offs)].tolist() == offs and (got_o[len(offs):] == NO_ERROR).all()
+    assert got_e[:13 * len(offs)].tobytes() == b"".join(want[1][o] for o in offs)
+    assert (got_e[13 * len(offs):] == 0xEE).all()
+    assert [vcfc.sparse_index_offset(p) for p in (0, 784, 1 << 55, (1 << 64) - 1)] == \
+        [SX.slot_offset(p) for p in (0, 784, 1 << 55, (1 << 64) - 1)]
+    # sizes-only decode and the gap fields
+    dwsb = vcfc.decode_sizes_workspace_size(n)
+    dws = torch.empty(dwsb, dtype=torch.uint8, device=dev)
+    loff = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    po = torch.empty(n, dtype=torch.int64, device=dev)
+    pl = torch.empty(n, dtype=torch.int32, device=dev)
+    cc = torch.empty(n, dtype=torch.int64, device=dev)
+    vcfc.decode_sizes_device(out.data_ptr(), int(r[n]), rec.data_ptr(), n, 2, loff.data_ptr(), po.data_ptr(),
+                             pl.data_ptr(), cc.data_ptr(), dws.data_ptr(), dwsb, err.data_ptr(), s)
+    torch.cuda.synchronize()
+    assert int(err.item()) == -1
+    lo, po, pl, cc = loff.cpu().tolist(), po.cpu().tolist(), pl.cpu().tolist(), cc.cpu().tolist()
+    data = v[hdr:]
+    got = b"".join(b"%s %d %d\n" % (data[po[i]:po[i] + pl[i]], lo[i + 1] - lo[i], cc[i]) for i in range(n))
+    assert lo[0] == 0 and lo[n] == sum(len(x) + 1 for x in lines)
+    if n <= 4097:
+        assert (OK, got, -1) == SX.gap_analysis(v)
+    else:   # (the restatement decodes line by line: compare with the input lines and the count rule)
+        ro = r.tolist()
+        assert got == b"".join(b"%s %d %d\n" % (lines[i].split(b"\t")[1], len(lines[i]) + 1,
+                                                 SX.compressed_count(data[ro[i]:ro[i + 1]], 2)) for i in range(n))
+
+
+def test_sparse_index_2504x4000(ctx, wd):
+    """2504 samples x 4000 sorted records: the indexed query equals the VCF's
+    own lines for ranges that start on a record, and gap-analysis equals the
+    sizes of the decompress output's lines."""
+    import random_vcf
+    buf = io.BytesIO()
+    random_vcf.generate(2504, 4000, buf)
+    vcf = buf.getvalue()
+    path = os.path.join(wd, "big.vcfc")
+    enc = ctx.compress_buffer(vcf)
+    with open(path, "wb") as f:
+        f.write(enc)
+    assert ctx.create_sparse_index(path) is False
+    slots, size = SX.read_sparse_file(path + ".vcfci-sparse")
+    lines = vcf[vcf.index(b"\n1\t") + 1:].split(b"\n")[:-1]
+    # POS = 10000 + 2 i: no two records share a slot
+    assert len(slots) == 4000 and size == SX.slot_offset(10000 + 2 * 3999) + 13
+    for a, b in ((0, 0), (17, 1017), (3990, 3999), (1234, 1233), (2047, 2049)):
+        q = "1:%d-%d" % (10000 + 2 * a, 10000 + 2 * b)
+        st, got = query_abi(ctx, path, q, wd)
+        assert st == OK and got == b"".join(l + b"\n" for l in lines[a:b + 1]), (a, b)
+    # a range that starts in a hole: from the next record on
+    st, got = query_abi(ctx, path, "1:10001-10006", wd)
+    assert st == OK and got == b"".join(l + b"\n" for l in lines[1:4])
+    txt = os.path.join(wd, "big_gap.txt")
+    ctx.gap_analysis(path, txt)
+    rows = open(txt, "rb").read().split(b"\n")[:-1]
+    dec = ctx.decompress(enc)
+    dl = dec[dec.index(b"\n1\t") + 1:].split(b"\n")[:-1]
+    h = X.header_end(enc)
+    assert len(rows) == 4000 == len(dl)
+    p = h
+    for i, row in enumerate(rows):
+        k = X.record_at(enc, p)
+        pos, size_, cnt = row.split(b" ")
+        assert pos == dl[i].split(b"\t")[1] and int(size_) == len(dl[i]) + 1, i
+        assert int(cnt) == SX.compressed_count(enc[p:p + k], 2504), i
+        p += k

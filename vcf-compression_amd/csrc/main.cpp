@@ -2,14 +2,19 @@
 // for the codec path: `main compress|decompress|sparsify <in> <out>` and
 // `main query|sparse-query <in> <query>`, and for the binned external index:
 // `main create-binned-index <bin-size> <in>` and
-// `main query-binned-index <in> <region>`.  Data lines are
+// `main query-binned-index <in> <region>`, for the sparse external index:
+// `main create-sparse-index <in>` and `main query-sparse-index <in> <region>`,
+// and `main gap-analysis <in>`.  Data lines are
 // encoded on the GPU through libvcfc.so.  Error messages mirror the
 // reference's exceptions (which terminate the reference process).
+#include <cerrno>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <fcntl.h>
 #include <sys/stat.h>
+#include <unistd.h>
 
 #include "vcfc.h"
 
@@ -17,7 +22,10 @@ static int usage() {
     fprintf(stderr, "./main [compress|decompress|sparsify] <input_file> <output_file>\n"
                     "./main [query|sparse-query] <input_file> <ref>[:<start>-<end>]\n"
                     "./main create-binned-index <bin-size> <compressed-filename>\n"
-                    "./main query-binned-index <compressed-filename> <region>\n");
+                    "./main query-binned-index <compressed-filename> <region>\n"
+                    "./main create-sparse-index <compressed-filename>\n"
+                    "./main query-sparse-index <compressed-filename> <region>\n"
+                    "./main gap-analysis <compressed-filename>\n");
     return 1;
 }
 
@@ -234,6 +242,119 @@ int main(int argc, char **argv) {
         vcfc_ctx_destroy(ctx);
         if (st != VCFC_OK) {
             fprintf(stderr, "terminate called after throwing an instance of 'std::runtime_error'\n"
+                            "  what():  %s\n", vcfc_strerror(st));
+            return 134;
+        }
+        return 0;
+    }
+    if (action == "create-sparse-index") {
+        // src/main.cpp:4144-4157 -> create_sparse_external_index (:854-999): writes <file>.vcfci-sparse
+        if (argc != 3) {
+            printf("Usage: ./main create-sparse-index <compressed-filename>\n");
+            return 1;
+        }
+        const std::string index = std::string(argv[2]) + ".vcfci-sparse";
+        if (!file_exists(argv[2])) {   // thrown before the index is created (:858-862)
+            perror("fopen");
+            fprintf(stderr, "terminate called after throwing an instance of 'std::runtime_error'\n"
+                            "  what():  Failed to open file: %s\n", argv[2]);
+            return 134;
+        }
+        vcfc_ctx *ctx = nullptr;
+        int st = vcfc_ctx_create(0, &ctx);
+        if (st != VCFC_OK) {
+            fprintf(stderr, "vcfc: %s\n", vcfc_strerror(st));
+            return 1;
+        }
+        int64_t err_record = -1;
+        int seek_failed = 0;
+        st = vcfc_create_sparse_index_file(ctx, argv[2], index.c_str(), &err_record, &seek_failed);
+        vcfc_ctx_destroy(ctx);
+        if (st != VCFC_OK) {
+            fprintf(stderr, "terminate called after throwing an instance of 'std::runtime_error'\n"
+                            "  what():  %s (record %lld)\n", vcfc_strerror(st), (long long)err_record);
+            return 134;
+        }
+        if (seek_failed) fprintf(stderr, "lseek: Invalid argument\n");   // perror("lseek"), then return (:954-959)
+        return 0;
+    }
+    if (action == "query-sparse-index") {
+        // src/main.cpp:4158-4177 -> query_sparse_external_index (:1002-1281)
+        if (argc != 4) {
+            printf("Usage: ./main query-sparse-index <compressed-filename> <region>\n");
+            return 1;
+        }
+        const std::string index = std::string(argv[2]) + ".vcfci-sparse";
+        const std::string q(argv[3]);
+        uint64_t ref_len = 0, start = 0, end = 0;
+        int has_range = 0;
+        const int pq = vcfc_parse_query(q.data(), q.size(), &ref_len, &has_range, &start, &end);
+        if (pq != 0) {
+            const size_t colon = q.find(':'), dash = q.find('-', colon + 1);
+            if (pq == 1) printf("Query must contain a dash character: <ref>:<start>-<end>\n");
+            else if (pq == 2) printf("Failed to parse int from start position: %s\n", q.substr(colon + 1, dash - colon - 1).c_str());
+            else printf("Failed to parse int from end position: %s\n", q.substr(dash + 1).c_str());
+            printf("Failed to parse query string: %s\n", q.c_str());
+            return 1;
+        }
+        // the reference's early returns, each with exit 0 (:1019-1047, :1077-1082)
+        if (!file_exists(argv[2])) {
+            errno = ENOENT;
+            perror("fopen");
+            return 0;
+        }
+        if (!file_exists(index.c_str())) return 0;
+        {
+            const int ifd = open(index.c_str(), O_RDONLY);
+            if (ifd < 0) {
+                perror("open");
+                return 0;
+            }
+            const off_t probe = lseek(ifd, 10000000, SEEK_DATA);
+            if (probe < 0) perror("fseek");   // (the reference's label)
+            close(ifd);
+            if (probe < 0) return 0;
+        }
+        if ((int64_t)vcfc_sparse_index_offset(has_range ? start : 0) < 0) {
+            errno = EINVAL;
+            perror("lseek");
+            return 0;
+        }
+        vcfc_ctx *ctx = nullptr;
+        int st = vcfc_ctx_create(0, &ctx);
+        if (st != VCFC_OK) {
+            fprintf(stderr, "vcfc: %s\n", vcfc_strerror(st));
+            return 1;
+        }
+        fflush(stdout);
+        st = vcfc_query_sparse_index_file(ctx, argv[2], index.c_str(), q.data(), ref_len, has_range, start, end, 1);
+        vcfc_ctx_destroy(ctx);
+        if (st != VCFC_OK) {
+            fprintf(stderr, "terminate called after throwing an instance of 'VcfValidationError'\n"
+                            "  what():  %s\n", vcfc_strerror(st));
+            return 134;
+        }
+        return 0;
+    }
+    if (action == "gap-analysis") {
+        // src/main.cpp:4035-4037 -> gap_analysis (:3931-3980): writes start-positions.txt in the
+        // current directory.  Without a file name the reference dies in std::string(nullptr); here: usage.
+        if (argc < 3) return usage();
+        if (!file_exists(argv[2])) {   // the reference reads from fd -1 and throws on the empty header
+            fprintf(stderr, "terminate called after throwing an instance of 'VcfValidationError'\n"
+                            "  what():  Failed to open file: %s\n", argv[2]);
+            return 134;
+        }
+        vcfc_ctx *ctx = nullptr;
+        int st = vcfc_ctx_create(0, &ctx);
+        if (st != VCFC_OK) {
+            fprintf(stderr, "vcfc: %s\n", vcfc_strerror(st));
+            return 1;
+        }
+        st = vcfc_gap_analysis_file(ctx, argv[2], "start-positions.txt");
+        vcfc_ctx_destroy(ctx);
+        if (st != VCFC_OK) {
+            fprintf(stderr, "terminate called after throwing an instance of 'VcfValidationError'\n"
                             "  what():  %s\n", vcfc_strerror(st));
             return 134;
         }

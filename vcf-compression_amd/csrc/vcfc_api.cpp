@@ -8,6 +8,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <cerrno>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -21,6 +22,7 @@
 #include "vcfc_device.h"
 #include "vcfc_index_driver.h"
 #include "vcfc_ingest_driver.h"
+#include "vcfc_sparse_index_driver.h"
 
 hipError_t vcfc_sparse_plan_launch(const uint8_t *recs, const uint64_t *rec_off, uint64_t n, uint64_t data_start,
                                    uint64_t *file_off, uint8_t *prefix, uint64_t *status, hipStream_t s);
@@ -1133,6 +1135,165 @@ int vcfc_query_binned_index_file(vcfc_ctx *c, const char *in_path, const char *i
                                B, c->stream, sink, 4ull << 20, &qs);
     trace_index(c, qs, (uint64_t)sb.st_size);
     close(fd);
+    return st;
+}
+
+// ---- sparse external index: create_sparse_external_index (reference
+// src/main.cpp:854-999), query_sparse_external_index (:1002-1281), and
+// gap_analysis (:3931-3980); drivers in vcfc_sparse_index_driver.h ------------
+
+uint64_t vcfc_sparse_index_workspace_size(uint64_t n_records) {
+    return vcfc_sparse_index_workspace_layout(n_records).total;
+}
+
+uint64_t vcfc_sparse_index_offset(uint64_t pos) { return vcfc_spx::slot_offset(pos); }
+
+int vcfc_sparse_index_device(const uint8_t *d_in, const uint64_t *d_rec_start, uint64_t n, uint64_t base_offset,
+                             uint8_t *d_entries, uint64_t *d_file_off, uint64_t *d_count, uint64_t *d_status,
+                             void *d_ws, uint64_t ws_bytes, uint64_t *d_err, void *stream) {
+    if ((n && (!d_in || !d_rec_start || !d_entries || !d_file_off || !d_ws)) || !d_count || !d_status || !d_err)
+        return VCFC_E_ARG;
+    const VcfcSparseIndexLayout L = vcfc_sparse_index_workspace_layout(n);
+    if (n && ws_bytes < L.total) return VCFC_E_NOSPACE;
+    return vcfc_sparse_index_build(d_in, d_rec_start, n, base_offset, d_entries, d_file_off, d_count, d_status,
+                                   static_cast<uint8_t *>(d_ws), L, d_err, static_cast<hipStream_t>(stream)) == hipSuccess
+               ? VCFC_OK : VCFC_E_HIP;
+}
+
+namespace {
+struct FdIndexWriter : vcfc_spx::Writer {
+    int fd;
+    explicit FdIndexWriter(int f) : fd(f) {}
+    int pwrite(const uint8_t *p, uint64_t k, uint64_t off) override {
+        while (k) {
+            const ssize_t w = ::pwrite(fd, p, k, (off_t)off);
+            if (w < 0 && errno == EINTR) continue;
+            if (w < 0) return errno == EINVAL || errno == EFBIG ? 1 : -1;   // past what the file system addresses
+            if (w == 0) return -1;
+            p += w; k -= (uint64_t)w; off += (uint64_t)w;
+        }
+        return 0;
+    }
+};
+struct FdIndexFile : vcfc_spx::IndexFile {
+    int fd;
+    explicit FdIndexFile(int f) : fd(f) {}
+    int64_t pread(uint8_t *dst, uint64_t off, uint64_t k) override { return vcfc_dec::sq_pread(fd, dst, k, off); }
+    int64_t seek_data(uint64_t off) override { return (int64_t)lseek(fd, (off_t)off, SEEK_DATA); }
+};
+}  // namespace
+
+int vcfc_create_sparse_index_file(vcfc_ctx *c, const char *in_path, const char *out_path, int64_t *err_record,
+                                  int *seek_failed) {
+    if (err_record) *err_record = -1;
+    if (seek_failed) *seek_failed = 0;
+    if (!c || !in_path || !out_path) return VCFC_E_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
+    MappedFile f;
+    int st = f.open_ro(in_path);
+    if (st) return st;
+    // DEFAULT_FILE_CREATE_FLAGS / _MODE: opened (truncated) before the input is parsed (:863)
+    const int fd = open(out_path, O_CREAT | O_TRUNC | O_RDWR, 0600);
+    if (fd < 0) return VCFC_E_IO;
+    CtxDecodeBuffers B(c);
+    FdIndexWriter W(fd);
+    vcfc_spx::CreateStats cs;
+    st = vcfc_spx::create_index(f.p, f.n, B, c->stream, W, err_record, seek_failed, &cs);
+    if (c->trace & VCFC_TRACE_INDEX)
+        fprintf(stderr, "create_sparse_index: %llu records, %llu entries, %llu pwrite calls%s\n",
+                (unsigned long long)cs.records, (unsigned long long)cs.entries, (unsigned long long)cs.pwrites,
+                cs.in_order ? " (record order)" : "");
+    if (close(fd) != 0 && !st) st = VCFC_E_IO;
+    return st;
+}
+
+int vcfc_query_sparse_index_file(vcfc_ctx *c, const char *in_path, const char *index_path, const char *ref,
+                                 uint64_t ref_len, int has_range, uint64_t start, uint64_t end, int out_fd) {
+    if (!c || !in_path || !index_path || (!ref && ref_len) || out_fd < 0) return VCFC_E_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
+    const int fd = open(in_path, O_RDONLY);
+    if (fd < 0) return VCFC_E_IO;
+    const int ifd = open(index_path, O_RDONLY);
+    struct stat sb;
+    if (ifd < 0 || fstat(fd, &sb) != 0) {
+        close(fd);
+        if (ifd >= 0) close(ifd);
+        return VCFC_E_IO;
+    }
+    auto sink = [&](const uint8_t *p, uint64_t k) {
+        while (k) {
+            const ssize_t w = write(out_fd, p, std::min<uint64_t>(k, 1ull << 30));
+            if (w <= 0) return false;
+            p += w;
+            k -= (uint64_t)w;
+        }
+        return true;
+    };
+    FdReader R(fd, (uint64_t)sb.st_size);
+    FdIndexFile I(ifd);
+    CtxDecodeBuffers B(c);
+    vcfc_idx::QueryStats qs;
+    const int st = vcfc_spx::query_index(R, I, reinterpret_cast<const uint8_t *>(ref), ref_len, has_range, start, end, B,
+                                         c->stream, sink, 4ull << 20, &qs);
+    if (c->trace & VCFC_TRACE_INDEX)
+        fprintf(stderr, "query_sparse_index: %llu windows, %llu bytes read of %llu, %llu records spanned\n",
+                (unsigned long long)qs.windows, (unsigned long long)qs.bytes, (unsigned long long)sb.st_size,
+                (unsigned long long)qs.records);
+    close(ifd);
+    close(fd);
+    return st;
+}
+
+uint64_t vcfc_decode_sizes_workspace_size(uint64_t n_records) { return vcfc_decode_workspace_layout(n_records).total; }
+
+int vcfc_decode_sizes_device(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_rec_start, uint64_t n,
+                             uint64_t sample_count, uint64_t *d_line_off, uint64_t *d_pos_off, uint32_t *d_pos_len,
+                             uint64_t *d_ccount, void *d_ws, uint64_t ws_bytes, uint64_t *d_err, void *stream) {
+    const bool fields = d_pos_off || d_pos_len || d_ccount;
+    if ((n && (!d_in || !d_rec_start)) || !d_line_off || !d_ws || !d_err ||
+        (fields && (!d_pos_off || !d_pos_len || !d_ccount)))
+        return VCFC_E_ARG;
+    const VcfcDecodeLayout L = vcfc_decode_workspace_layout(n);
+    if (ws_bytes < L.total) return VCFC_E_NOSPACE;
+    uint8_t *ws = static_cast<uint8_t *>(d_ws);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    VcfcDecodeArgs a;
+    a.in = d_in; a.n_bytes = in_bytes; a.rec_start = d_rec_start; a.select = nullptr; a.n = n; a.S = sample_count;
+    a.out = nullptr; a.out_cap = 0; a.line_off = d_line_off;
+    a.st = reinterpret_cast<uint32_t *>(ws + L.st);
+    a.line_size = reinterpret_cast<uint32_t *>(ws + L.line_size);
+    a.end = reinterpret_cast<uint64_t *>(ws + L.end);
+    a.seq_list = reinterpret_cast<uint32_t *>(ws + L.seq_list);
+    a.seq_count = reinterpret_cast<uint32_t *>(ws + L.seq_count);
+    a.err = d_err;   // the caller's word: the plan resets it, the field pass shares it
+    a.partials = reinterpret_cast<uint64_t *>(ws + L.partials);
+    if (vcfc_decode_plan(a, true, s) != hipSuccess) return VCFC_E_HIP;
+    if (fields && vcfc_gap_fields(d_in, d_rec_start, n, sample_count, d_pos_off, d_pos_len, d_ccount, d_err, s) != hipSuccess)
+        return VCFC_E_HIP;
+    return VCFC_OK;
+}
+
+int vcfc_gap_analysis_file(vcfc_ctx *c, const char *in_path, const char *out_path) {
+    if (!c || !in_path || !out_path) return VCFC_E_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
+    MappedFile f;
+    int st = f.open_ro(in_path);
+    if (st) return st;
+    // the reference opens its output after the header parse (:3939-3948): a
+    // header it throws on leaves no file
+    uint64_t data_off = 0;
+    if ((st = vcfc_dec::parse_header(f.p, f.n, &data_off, nullptr))) return st;
+    const int fd = open(out_path, O_CREAT | O_TRUNC | O_WRONLY, 0644);
+    if (fd < 0) return VCFC_E_IO;
+    uint64_t o = 0;
+    auto sink = [&](const uint8_t *p, uint64_t k) {
+        if (write_all_at(fd, p, k, o) != VCFC_OK) return false;
+        o += k;
+        return true;
+    };
+    CtxDecodeBuffers B(c);
+    st = vcfc_spx::gap_analysis(f.p, f.n, B, c->stream, sink, nullptr);
+    if (close(fd) != 0 && !st) st = VCFC_E_IO;
     return st;
 }
 

@@ -321,3 +321,35 @@ hipError_t vcfc_index_build(const uint8_t *in, const uint64_t *rec_start, uint64
 hipError_t vcfc_index_compare(const uint8_t *ref_idx, const uint64_t *pos, const uint64_t *end, uint64_t n,
                               uint32_t qidx, uint64_t qstart, uint64_t qend, uint8_t *flag, uint64_t *first_after,
                               hipStream_t s);
+
+// ---------------------------------------------------------------------------
+// Sparse external index (vcfc_sparse_index.hip; reference
+// create_sparse_external_index, src/main.cpp:854-999, and
+// query_sparse_external_index, :1002-1281).
+struct VcfcSparseIndexLayout {
+    uint64_t ref_idx, pos, off, keep, eno, partials, total;
+};
+VcfcSparseIndexLayout vcfc_sparse_index_workspace_layout(uint64_t n);
+// one lane per record: ref_idx and POS.  walk == 0: create's rules (five TABs
+// inside the record; eight and compute_end_position's throws when ALT holds
+// '<'); walk != 0: the query walk's (CHROM and POS only).  err = min over
+// records of (i << 8 | code), code 2 = the reference throws, 3 = the TABs
+// this action reads do not all lie inside the record
+hipError_t vcfc_sparse_index_span(const uint8_t *in, const uint64_t *rec_start, uint64_t n, int walk, uint8_t *ref_idx,
+                                  uint64_t *pos, uint64_t *err, hipStream_t s);
+// span + slot offsets (300000000 + pos) * 256 + duplicate-slot resolution +
+// the kept entries {u8 ref_idx, u32 pos, u64 base_offset + rec_start[i]} and
+// their offsets, densely (entries: 13 n bytes, file_off: n words); *count =
+// kept entries; status[1] = 1: some offset decreases (the kept set is not the
+// reference's; write every record in order), status[2] = the first record
+// whose offset is negative as off_t (~0: none).  No host synchronisation.
+hipError_t vcfc_sparse_index_build(const uint8_t *in, const uint64_t *rec_start, uint64_t n, uint64_t base_offset,
+                                   uint8_t *entries, uint64_t *file_off, uint64_t *count, uint64_t *status,
+                                   uint8_t *ws, const VcfcSparseIndexLayout &L, uint64_t *err, hipStream_t s);
+// gap-analysis (reference src/main.cpp:3931-3980), one lane per record: the
+// location of the line's POS text (offset into `in`, length) and the
+// reference's compressed count (line_byte_count, src/compress.cpp:764-968).
+// err is NOT reset: atomicMin of (i << 8 | 3) for a record the walk refuses,
+// so it shares the word of the decode plan that sizes the same records.
+hipError_t vcfc_gap_fields(const uint8_t *in, const uint64_t *rec_start, uint64_t n, uint64_t S, uint64_t *pos_off,
+                           uint32_t *pos_len, uint64_t *ccount, uint64_t *err, hipStream_t s);

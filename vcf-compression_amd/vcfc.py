@@ -6,6 +6,8 @@ Mirrors the reference's operator interface for the encode path:
   decompress / decompress_file                 (reference src/compress.cpp:1214-1257)
   parse_coordinate_string, query / query_file  (reference src/main.cpp:3777-4026)
   create_binned_index / query_binned_index     (reference src/main.cpp:1284-1637, 2974-3349)
+  create_sparse_index / query_sparse_index     (reference src/main.cpp:854-999, 1002-1281)
+  gap_analysis                                 (reference src/main.cpp:3931-3980)
 Errors raise VcfValidationError / RuntimeError like the reference's exceptions
 (src/utils.hpp:117-123, src/compress.cpp:9-11,231-234).
 
@@ -45,6 +47,9 @@ EXPORTS = [
     "vcfc_index_workspace_size", "vcfc_binned_index_device", "vcfc_record_span_device",
     "vcfc_create_binned_index_buffer", "vcfc_create_binned_index_file",
     "vcfc_query_binned_index_buffer", "vcfc_query_binned_index_file",
+    "vcfc_sparse_index_workspace_size", "vcfc_sparse_index_offset", "vcfc_sparse_index_device",
+    "vcfc_create_sparse_index_file", "vcfc_query_sparse_index_file",
+    "vcfc_decode_sizes_workspace_size", "vcfc_decode_sizes_device", "vcfc_gap_analysis_file",
 ]
 LINE_INDEX_HOP, LINE_INDEX_SCAN = 0, 1                       # include/vcfc.h VCFC_LINE_INDEX_*
 TRACE_INGEST, TRACE_DEVICE, TRACE_SPARSE_QUERY = 1, 2, 4     # include/vcfc.h VCFC_TRACE_*
@@ -94,12 +99,25 @@ def lib():
             "vcfc_query_binned_index_buffer": [vp, vp, u64, vp, u64, ctypes.c_char_p, u64, ctypes.c_int, u64, u64, vp,
                                                u64, ctypes.POINTER(u64)],
             "vcfc_query_binned_index_file": [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, u64, ctypes.c_int,
-                                             u64, u64, ctypes.c_int]}
+                                             u64, u64, ctypes.c_int],
+            # the sparse external index and gap-analysis
+            "vcfc_sparse_index_workspace_size": [u64],
+            "vcfc_sparse_index_offset": [u64],
+            "vcfc_sparse_index_device": [vp, vp, u64, u64, vp, vp, vp, vp, vp, u64, vp, vp],
+            "vcfc_create_sparse_index_file": [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(i64),
+                                              ctypes.POINTER(ctypes.c_int)],
+            "vcfc_query_sparse_index_file": [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, u64, ctypes.c_int,
+                                             u64, u64, ctypes.c_int],
+            "vcfc_decode_sizes_workspace_size": [u64],
+            "vcfc_decode_sizes_device": [vp, u64, vp, u64, u64, vp, vp, vp, vp, vp, u64, vp, vp],
+            "vcfc_gap_analysis_file": [vp, ctypes.c_char_p, ctypes.c_char_p]}
     for name, args in late.items():
         if hasattr(L, name):
             getattr(L, name).argtypes = args
-    if hasattr(L, "vcfc_index_workspace_size"):
-        L.vcfc_index_workspace_size.restype = u64
+    for name in ("vcfc_index_workspace_size", "vcfc_sparse_index_workspace_size", "vcfc_sparse_index_offset",
+                 "vcfc_decode_sizes_workspace_size"):
+        if hasattr(L, name):
+            getattr(L, name).restype = u64
     L.vcfc_record_hash_device.argtypes = [vp, vp, u64, vp, vp]
     L.vcfc_compress_range.argtypes = [vp, ctypes.c_char_p, u64, u64, ctypes.c_int, u64, ctypes.POINTER(u64),
                                       ctypes.POINTER(i64), ctypes.POINTER(u64)]
@@ -530,6 +548,46 @@ class Context:
                                                         query.reference_name, len(query.reference_name),
                                                         int(query.has_range), query.start, query.end, out_fd))
 
+    # -- sparse external index (reference src/main.cpp:854-999, 1002-1281) and gap-analysis (:3931-3980) --
+    def create_sparse_index_status(self, in_path, index_path=None):
+        """create_sparse_external_index: writes in_path + ".vcfci-sparse" (or
+        index_path), a sparse file with the 13-byte entry of a record at
+        offset (300000000 + POS) * 256.  Returns (status, err_record,
+        seek_failed): E_FORMAT where the reference throws (err_record = the
+        record), seek_failed where its lseek to a slot fails (status OK);
+        the entries of the records before it are in the file either way."""
+        index_path = index_path or in_path + ".vcfci-sparse"
+        er, sf = ctypes.c_int64(-1), ctypes.c_int(0)
+        st = _need("vcfc_create_sparse_index_file")(self._h, in_path.encode(), index_path.encode(), ctypes.byref(er),
+                                                    ctypes.byref(sf))
+        return st, er.value, sf.value
+
+    def create_sparse_index(self, in_path, index_path=None):
+        """`main create-sparse-index <in_path>`, raising where the reference
+        throws; returns True where its lseek failed and the index is partial."""
+        st, er, sf = self.create_sparse_index_status(in_path, index_path)
+        raise_for(st, "record %d" % er if er >= 0 else "")
+        return bool(sf)
+
+    def query_sparse_index(self, in_path, query, out_fd=1, index_path=None):
+        """`main query-sparse-index <in_path> <region>`: lines to out_fd."""
+        if not isinstance(query, VcfCoordinateQuery):
+            query = parse_coordinate_string(query)
+        index_path = index_path or in_path + ".vcfci-sparse"
+        raise_for(_need("vcfc_query_sparse_index_file")(self._h, in_path.encode(), index_path.encode(),
+                                                        query.reference_name, len(query.reference_name),
+                                                        int(query.has_range), query.start, query.end, out_fd))
+
+    @staticmethod
+    def sparse_index_device(*args, **kw):
+        """The module's sparse_index_device (no context state is used)."""
+        return sparse_index_device(*args, **kw)
+
+    def gap_analysis(self, in_path, out_path="start-positions.txt"):
+        """`main gap-analysis <in_path>`: one line "<POS> <decoded line bytes>
+        <compressed count>" per record into out_path."""
+        raise_for(_need("vcfc_gap_analysis_file")(self._h, in_path.encode(), out_path.encode()))
+
     def sparsify_file(self, in_path, out_path):
         """sparsify_file (reference src/sparse.cpp:290-580)."""
         raise_for(lib().vcfc_sparsify_file(self._h, in_path.encode(), out_path.encode()))
@@ -654,6 +712,36 @@ def synth_rows_device(d_buf, d_line_off, n, d_prefix, d_prefix_off, d_row_af, sa
 def record_hash_device(d_recs, d_rec_off, n, d_hash, stream=0):
     """Per-record 64-bit digests on the GPU (include/vcfc.h vcfc_record_hash_device)."""
     raise_for(lib().vcfc_record_hash_device(d_recs, d_rec_off, n, d_hash, stream))
+
+
+def sparse_index_workspace_size(n_records):
+    return int(_need("vcfc_sparse_index_workspace_size")(n_records))
+
+
+def sparse_index_offset(pos):
+    """The file offset of the slot of `pos` in a sparse external index."""
+    return int(_need("vcfc_sparse_index_offset")(pos))
+
+
+def sparse_index_device(d_in, d_rec_start, n, base_offset, d_entries, d_file_off, d_count, d_status, d_ws, ws_bytes,
+                        d_err, stream=0):
+    """The kept entries of device-resident records and their file offsets
+    (include/vcfc.h vcfc_sparse_index_device); enqueued on `stream`."""
+    raise_for(_need("vcfc_sparse_index_device")(d_in, d_rec_start, n, base_offset, d_entries, d_file_off, d_count,
+                                                d_status, d_ws, ws_bytes, d_err, stream))
+
+
+def decode_sizes_workspace_size(n_records):
+    return int(_need("vcfc_decode_sizes_workspace_size")(n_records))
+
+
+def decode_sizes_device(d_in, in_bytes, d_rec_start, n, sample_count, d_line_off, d_pos_off, d_pos_len, d_ccount,
+                        d_ws, ws_bytes, d_err, stream=0):
+    """Decoded line offsets without the lines, and per record the POS text
+    location and the reference's compressed count (include/vcfc.h
+    vcfc_decode_sizes_device); enqueued on `stream`."""
+    raise_for(_need("vcfc_decode_sizes_device")(d_in, in_bytes, d_rec_start, n, sample_count, d_line_off, d_pos_off,
+                                                d_pos_len, d_ccount, d_ws, ws_bytes, d_err, stream))
 
 
 def index_workspace_size(n_records):
