@@ -429,6 +429,62 @@ int vcfc_decode_sizes_device(const uint8_t *d_in, uint64_t in_bytes, const uint6
  * VCFC_E_FORMAT, the lines of the records before it written. */
 int vcfc_gap_analysis_file(vcfc_ctx *ctx, const char *in_vcfc, const char *out_txt);
 
+/* ---- sample subset: decompress-samples, query-samples (no
+ * reference counterpart: the oracle is a cut of the reference's own decode) --
+ * `cols`: K >= 1 distinct 0-based sample columns, each < S (the '#CHROM'
+ * line's sample count), in output order.  The output header is every '##'
+ * line, then the '#CHROM' line's first 9 fields and the chosen names.  A
+ * record is regular when both length headers carry bits 11, REQ is
+ * non-empty, inside the record, holds exactly 9 TABs and no NUL, the sample
+ * section is a sequence of run bytes (a count of 0 yields nothing) and
+ * escapes (tokens ended by TAB, the record's very last one by the closing
+ * LF) whose token counts add up to exactly S with no item passing S, and
+ * the LF after them is the record's last byte.  Its line is REQ, the chosen
+ * tokens joined by TAB, LF.  The call stops with VCFC_E_FORMAT at the first
+ * record that is not regular, or where the LEN hops stop with 8 or more
+ * bytes left; the output holds the header and every line before it.
+ * VCFC_E_FORMAT with nothing written for a header the decoder refuses;
+ * VCFC_E_ARG with nothing written for K = 0, a column >= S, a column listed
+ * twice.  The query variants write no header, match records exactly as
+ * vcfc_query_buffer does and ask only matching records to be regular; a
+ * match error (codes 2, 3 of vcfc_query_match_device) at record k stops
+ * there with VCFC_E_FORMAT.  Buffer variants: VCFC_E_NOSPACE if out_cap is
+ * short (*out_len = size needed); vcfc_query_samples_file writes to out_fd. */
+int vcfc_decompress_samples_buffer(vcfc_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const uint32_t *cols,
+                                   uint64_t n_cols, uint8_t *out, uint64_t out_cap, uint64_t *out_len);
+int vcfc_decompress_samples_file(vcfc_ctx *ctx, const char *in_vcfc, const char *out_vcf, const uint32_t *cols,
+                                 uint64_t n_cols);
+int vcfc_query_samples_buffer(vcfc_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const char *ref, uint64_t ref_len,
+                              int has_range, uint64_t start, uint64_t end, const uint32_t *cols, uint64_t n_cols,
+                              uint8_t *out, uint64_t out_cap, uint64_t *out_len);
+int vcfc_query_samples_file(vcfc_ctx *ctx, const char *in_vcfc, const char *ref, uint64_t ref_len, int has_range,
+                            uint64_t start, uint64_t end, const uint32_t *cols, uint64_t n_cols, int out_fd);
+/* Resolve a comma-separated list of sample names (names[0, names_len))
+ * against the '#CHROM' line of a .vcfc (host bytes; the header is enough):
+ * cols[0, *n_cols) in list order.  Where the header repeats a name its first
+ * occurrence wins.  VCFC_E_ARG with *bad_off = the offset in `names` of a
+ * name the header does not hold, or of the second listing of a name;
+ * VCFC_E_NOSPACE if cols_cap is short (*n_cols = columns needed);
+ * VCFC_E_FORMAT for a header the decoder refuses. */
+int vcfc_sample_columns(const uint8_t *in, uint64_t in_bytes, const char *names, uint64_t names_len, uint32_t *cols,
+                        uint64_t cols_cap, uint64_t *n_cols, uint64_t *bad_off);
+/* Device-resident subset decode, exact in one call: the lines of records
+ * d_in[d_rec_start[i], d_rec_start[i+1]) (d_select nullable: records with
+ * d_select[i] == 0 get no line and are not checked) at d_out +
+ * d_line_off[i]; d_line_off[n] = total.  `cols` is host memory: it is
+ * checked (VCFC_E_ARG as above, also for samples >= 2^31), sorted and
+ * uploaded into the workspace before the kernels are enqueued on `stream`
+ * (the upload synchronises the stream once).  As in the decoder, records
+ * are loaded in whole dwords: up to 3 bytes past the last record's end must
+ * be readable.  *d_err = ~0, or min over
+ * records of (i << 8 | 3) where a record is not regular (it and the records
+ * after it have no meaningful line), (i << 8 | 0xFF): out_cap too small. */
+uint64_t vcfc_subset_workspace_size(uint64_t n_records, uint64_t n_cols);
+int vcfc_decode_samples_device(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_rec_start,
+                               const uint8_t *d_select, uint64_t n, uint64_t samples, const uint32_t *cols,
+                               uint64_t n_cols, uint8_t *d_out, uint64_t out_cap, uint64_t *d_line_off, void *d_ws,
+                               uint64_t ws_bytes, uint64_t *d_err, void *stream);
+
 /* ---- sparse layout: sparsify_file (reference src/sparse.cpp:290-580) -------
  * Record i of the .vcfc goes to data_start + (300e6 + POS_i) * 16384
  * (compute_sparse_offset, src/sparse.cpp:18-51) behind a 16-byte prefix

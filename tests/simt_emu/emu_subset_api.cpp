@@ -1,0 +1,103 @@
+// TEST INFRASTRUCTURE ONLY: C entry points that run the sample-subset kernels
+// (csrc/vcfc_subset.hip) and their host driver (csrc/vcfc_subset_driver.h) on
+// the fiber emulator, with host memory standing in for HBM.
+#include <algorithm>
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "vcfc_device.h"
+#include "vcfc_subset_driver.h"
+#include "emu.h"
+
+namespace {
+struct HostBuffers : vcfc_dec::Buffers {
+    std::vector<uint8_t> b[N_SLOTS];
+    void *get(int slot, uint64_t bytes) override {
+        if (b[slot].size() < bytes) b[slot].assign(bytes, 0xCD);   // poison
+        return b[slot].data();
+    }
+};
+
+struct Call {
+    std::vector<uint8_t> hdr;
+    std::vector<uint32_t> csort, rank;
+    uint64_t data_off = 0, S = 0;
+    int prepare(const uint8_t *in, uint64_t n, const uint32_t *cols, uint64_t K) {
+        int st = vcfc_sub::subset_header(in, n, cols, K, hdr, &data_off, &S);
+        if (!st) st = vcfc_sub::sort_columns(cols, K, S, csort, rank);
+        return st;
+    }
+};
+}  // namespace
+
+// decompress-samples over a whole .vcfc (the C ABI's control flow)
+extern "C" int emu_subset_decompress(const uint8_t *in, uint64_t n, const uint32_t *cols, uint64_t K, uint8_t *out,
+                                     uint64_t cap, uint64_t *out_len, uint64_t out_batch) {
+    *out_len = 0;
+    Call c;
+    int st = c.prepare(in, n, cols, K);
+    if (st) return st;
+    uint64_t o = 0;
+    auto sink = [&](const uint8_t *p, uint64_t k) {
+        if (o + k > cap) return false;
+        memcpy(out + o, p, k);
+        o += k;
+        return true;
+    };
+    sink(c.hdr.data(), c.hdr.size());
+    HostBuffers B;
+    st = vcfc_sub::decode_section(in + c.data_off, n - c.data_off, c.S, c.csort, c.rank, B, nullptr, sink, out_batch);
+    *out_len = o;
+    return st;
+}
+
+// query-samples over a whole .vcfc
+extern "C" int emu_subset_query(const uint8_t *in, uint64_t n, const uint8_t *ref, uint64_t ref_len, int has_range,
+                                uint64_t qstart, uint64_t qend, const uint32_t *cols, uint64_t K, uint8_t *out,
+                                uint64_t cap, uint64_t *out_len, uint64_t out_batch) {
+    *out_len = 0;
+    Call c;
+    int st = c.prepare(in, n, cols, K);
+    if (st) return st;
+    uint64_t o = 0;
+    auto sink = [&](const uint8_t *p, uint64_t k) {
+        if (o + k > cap) return false;
+        memcpy(out + o, p, k);
+        o += k;
+        return true;
+    };
+    HostBuffers B;
+    st = vcfc_sub::query_section(in + c.data_off, n - c.data_off, c.S, c.csort, c.rank, ref, ref_len, has_range, qstart,
+                                 qend, B, nullptr, sink, out_batch);
+    *out_len = o;
+    return st;
+}
+
+// the device entry's kernels on records[rec[0], rec[n]): plan + write in one
+// go; out has out_cap bytes (+ the caller's canary), *err the error word
+extern "C" int emu_subset_device(const uint8_t *recs, const uint64_t *rec, const uint8_t *select, uint64_t n, uint64_t S,
+                                 const uint32_t *cols, uint64_t K, uint8_t *out, uint64_t out_cap, uint64_t *line_off,
+                                 uint64_t *err) {
+    std::vector<uint32_t> csort, rank;
+    if (vcfc_sub::sort_columns(cols, K, S, csort, rank)) return vcfc_sub::ST_E_ARG;
+    const VcfcSubsetLayout L = vcfc_subset_workspace_layout(n, K);
+    std::vector<uint8_t> ws(L.total + 64, 0xCD);
+    std::vector<uint8_t> in(recs, recs + (n ? rec[n] : 0));
+    in.resize(in.size() + 64, 0xCD);
+    VcfcSubsetArgs a;
+    a.in = in.data(); a.n_bytes = n ? rec[n] : 0; a.rec_start = rec; a.select = select; a.n = n; a.S = S;
+    a.K = (uint32_t)K; a.out = out; a.out_cap = out_cap; a.line_off = line_off;
+    vcfc_subset_args_workspace(a, ws.data(), L);
+    a.err = err;
+    memcpy(ws.data() + L.csort, csort.data(), 4 * K);
+    memcpy(ws.data() + L.rank, rank.data(), 4 * K);
+    if (vcfc_subset_plan(a, nullptr) != hipSuccess) return vcfc_sub::ST_E_HIP;
+    return vcfc_subset_write(a, 0, n, nullptr) == hipSuccess ? 0 : vcfc_sub::ST_E_HIP;
+}
+
+extern "C" int emu_sample_columns(const uint8_t *in, uint64_t n, const char *names, uint64_t names_len, uint32_t *cols,
+                                  uint64_t cols_cap, uint64_t *n_cols, uint64_t *bad_off) {
+    return vcfc_sub::sample_columns(in, n, names, names_len, cols, cols_cap, n_cols, bad_off);
+}

@@ -4,14 +4,18 @@
 // `main create-binned-index <bin-size> <in>` and
 // `main query-binned-index <in> <region>`, for the sparse external index:
 // `main create-sparse-index <in>` and `main query-sparse-index <in> <region>`,
-// and `main gap-analysis <in>`.  Data lines are
+// and `main gap-analysis <in>`; beyond the reference, the sample subset:
+// `main decompress-samples <in> <out> <names>` and
+// `main query-samples <in> <query> <names>`.  Data lines are
 // encoded on the GPU through libvcfc.so.  Error messages mirror the
 // reference's exceptions (which terminate the reference process).
 #include <cerrno>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <algorithm>
 #include <string>
+#include <vector>
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -25,8 +29,48 @@ static int usage() {
                     "./main query-binned-index <compressed-filename> <region>\n"
                     "./main create-sparse-index <compressed-filename>\n"
                     "./main query-sparse-index <compressed-filename> <region>\n"
-                    "./main gap-analysis <compressed-filename>\n");
+                    "./main gap-analysis <compressed-filename>\n"
+                    "./main decompress-samples <input_file> <output_file> <name>[,<name>...]\n"
+                    "./main query-samples <input_file> <ref>[:<start>-<end>] <name>[,<name>...]\n");
     return 1;
+}
+
+// The sample columns of a comma-separated name list, resolved against the
+// header of `path` (read as a growing prefix of the file).  0: cols filled;
+// 1: a message was printed (unknown / duplicate name); VCFC_E_FORMAT /
+// VCFC_E_IO otherwise.
+static int resolve_samples(const char *path, const std::string &names, std::vector<uint32_t> &cols) {
+    const int fd = open(path, O_RDONLY);
+    if (fd < 0) return VCFC_E_IO;
+    struct stat sb;
+    if (fstat(fd, &sb) != 0) { close(fd); return VCFC_E_IO; }
+    const uint64_t fsize = (uint64_t)sb.st_size;
+    std::vector<uint8_t> buf;
+    cols.resize(names.size() + 1);
+    int st = VCFC_E_FORMAT;
+    uint64_t n_cols = 0, bad = 0;
+    for (uint64_t want = 1ull << 20;; want *= 4) {
+        buf.resize(std::min<uint64_t>(want, fsize));
+        uint64_t got = 0;
+        while (got < buf.size()) {
+            const ssize_t r = pread(fd, buf.data() + got, buf.size() - got, (off_t)got);
+            if (r <= 0) break;
+            got += (uint64_t)r;
+        }
+        st = vcfc_sample_columns(buf.data(), got, names.data(), names.size(), cols.data(), cols.size(), &n_cols, &bad);
+        if (st != VCFC_E_FORMAT || buf.size() >= fsize) break;   // (a header cut short does not parse: read more)
+    }
+    close(fd);
+    if (st == VCFC_E_ARG) {
+        const size_t e = names.find(',', bad);
+        const std::string name = names.substr(bad, e == std::string::npos ? e : e - bad);
+        // every name before this one resolved: listed there too, it is a duplicate
+        const bool dup = ("," + names.substr(0, bad)).find("," + name + ",") != std::string::npos;
+        printf("%s sample name: %s\n", dup ? "Duplicate" : "Unknown", name.c_str());
+        return 1;
+    }
+    cols.resize(st == VCFC_OK ? n_cols : 0);
+    return st;
 }
 
 static bool file_exists(const char *p) {
@@ -357,6 +401,57 @@ int main(int argc, char **argv) {
             fprintf(stderr, "terminate called after throwing an instance of 'VcfValidationError'\n"
                             "  what():  %s\n", vcfc_strerror(st));
             return 134;
+        }
+        return 0;
+    }
+    if (action == "decompress-samples" || action == "query-samples") {
+        // no reference counterpart: the chosen samples' columns of `decompress` / `query`
+        const bool query = action == "query-samples";
+        if (argc < 5) return usage();
+        if (!file_exists(argv[2])) printf("Input file does not exist: %s\n", argv[2]);
+        if (!query && std::string(argv[2]) == argv[3]) {
+            fprintf(stderr, "terminate called after throwing an instance of 'std::runtime_error'\n"
+                            "  what():  input and output file are the same\n");
+            return 134;
+        }
+        const std::string q(query ? argv[3] : "");
+        uint64_t ref_len = 0, start = 0, end = 0;
+        int has_range = 0;
+        if (query) {
+            const int pq = vcfc_parse_query(q.data(), q.size(), &ref_len, &has_range, &start, &end);
+            if (pq != 0) {
+                const size_t colon = q.find(':'), dash = q.find('-', colon + 1);
+                if (pq == 1) printf("Query must contain a dash character: <ref>:<start>-<end>\n");
+                else if (pq == 2) printf("Failed to parse int from start position: %s\n", q.substr(colon + 1, dash - colon - 1).c_str());
+                else printf("Failed to parse int from end position: %s\n", q.substr(dash + 1).c_str());
+                printf("Failed to parse query string: %s\n", q.c_str());
+                return 1;
+            }
+        }
+        std::vector<uint32_t> cols;
+        int st = resolve_samples(argv[2], argv[4], cols);
+        if (st == 1) return 1;   // unknown / duplicate name: message printed, nothing written
+        if (st == VCFC_OK) {
+            vcfc_ctx *ctx = nullptr;
+            st = vcfc_ctx_create(0, &ctx);
+            if (st != VCFC_OK) {
+                fprintf(stderr, "vcfc: %s\n", vcfc_strerror(st));
+                return 1;
+            }
+            fflush(stdout);
+            st = query ? vcfc_query_samples_file(ctx, argv[2], q.data(), ref_len, has_range, start, end, cols.data(),
+                                                 cols.size(), 1)
+                       : vcfc_decompress_samples_file(ctx, argv[2], argv[3], cols.data(), cols.size());
+            vcfc_ctx_destroy(ctx);
+        }
+        if (st == VCFC_E_FORMAT) {
+            fprintf(stderr, "terminate called after throwing an instance of 'VcfValidationError'\n"
+                            "  what():  %s\n", vcfc_strerror(st));
+            return 134;
+        }
+        if (st != VCFC_OK) {
+            fprintf(stderr, "Error in decompression of file: %s\n", vcfc_strerror(st));
+            return 1;
         }
         return 0;
     }

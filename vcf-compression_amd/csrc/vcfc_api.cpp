@@ -23,6 +23,7 @@
 #include "vcfc_index_driver.h"
 #include "vcfc_ingest_driver.h"
 #include "vcfc_sparse_index_driver.h"
+#include "vcfc_subset_driver.h"
 
 hipError_t vcfc_sparse_plan_launch(const uint8_t *recs, const uint64_t *rec_off, uint64_t n, uint64_t data_start,
                                    uint64_t *file_off, uint8_t *prefix, uint64_t *status, hipStream_t s);
@@ -1295,6 +1296,159 @@ int vcfc_gap_analysis_file(vcfc_ctx *c, const char *in_path, const char *out_pat
     st = vcfc_spx::gap_analysis(f.p, f.n, B, c->stream, sink, nullptr);
     if (close(fd) != 0 && !st) st = VCFC_E_IO;
     return st;
+}
+
+// ---- sample subset; drivers in vcfc_subset_driver.h ---------
+
+namespace {
+// header + sorted columns of a subset call; the status where either fails
+struct SubsetCall {
+    std::vector<uint8_t> hdr;
+    std::vector<uint32_t> csort, rank;
+    uint64_t data_off = 0, S = 0;
+    int prepare(const uint8_t *in, uint64_t n, const uint32_t *cols, uint64_t K) {
+        int st = vcfc_sub::subset_header(in, n, cols, K, hdr, &data_off, &S);
+        if (!st) st = vcfc_sub::sort_columns(cols, K, S, csort, rank);
+        return st;
+    }
+};
+}  // namespace
+
+int vcfc_sample_columns(const uint8_t *in, uint64_t n, const char *names, uint64_t names_len, uint32_t *cols,
+                        uint64_t cols_cap, uint64_t *n_cols, uint64_t *bad_off) {
+    if ((!in && n) || (!names && names_len) || (!cols && cols_cap) || !n_cols || !bad_off) return VCFC_E_ARG;
+    *n_cols = 0;
+    *bad_off = 0;
+    return vcfc_sub::sample_columns(in, n, names, names_len, cols, cols_cap, n_cols, bad_off);
+}
+
+int vcfc_decompress_samples_buffer(vcfc_ctx *c, const uint8_t *in, uint64_t n, const uint32_t *cols, uint64_t n_cols,
+                                   uint8_t *out, uint64_t out_cap, uint64_t *out_len) {
+    if (!c || (!in && n) || (!out && out_cap) || !out_len) return VCFC_E_ARG;
+    *out_len = 0;
+    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
+    SubsetCall sc;
+    int st = sc.prepare(in, n, cols, n_cols);
+    if (st) return st;
+    uint64_t o = 0;
+    bool fits = true;
+    auto sink = [&](const uint8_t *p, uint64_t k) {
+        if (fits && o + k <= out_cap) memcpy(out + o, p, k);
+        else fits = false;
+        o += k;
+        return true;
+    };
+    sink(sc.hdr.data(), sc.hdr.size());
+    CtxDecodeBuffers B(c);
+    st = vcfc_sub::decode_section(in + sc.data_off, n - sc.data_off, sc.S, sc.csort, sc.rank, B, c->stream, sink);
+    *out_len = o;
+    if (!fits) return VCFC_E_NOSPACE;
+    return st;
+}
+
+int vcfc_decompress_samples_file(vcfc_ctx *c, const char *in_path, const char *out_path, const uint32_t *cols,
+                                 uint64_t n_cols) {
+    if (!c || !in_path || !out_path) return VCFC_E_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
+    MappedFile f;
+    int st = f.open_ro(in_path);
+    if (st) return st;
+    SubsetCall sc;
+    if ((st = sc.prepare(f.p, f.n, cols, n_cols))) return st;   // nothing written
+    const int fd = open(out_path, O_CREAT | O_TRUNC | O_WRONLY, 0644);
+    if (fd < 0) return VCFC_E_IO;
+    uint64_t o = 0;
+    auto sink = [&](const uint8_t *p, uint64_t k) {
+        if (write_all_at(fd, p, k, o)) return false;
+        o += k;
+        return true;
+    };
+    if (!sink(sc.hdr.data(), sc.hdr.size())) st = VCFC_E_IO;
+    if (!st) {
+        CtxDecodeBuffers B(c);
+        st = vcfc_sub::decode_section(f.p + sc.data_off, f.n - sc.data_off, sc.S, sc.csort, sc.rank, B, c->stream, sink);
+    }
+    if (close(fd) != 0 && !st) st = VCFC_E_IO;
+    return st;
+}
+
+int vcfc_query_samples_buffer(vcfc_ctx *c, const uint8_t *in, uint64_t n, const char *ref, uint64_t ref_len,
+                              int has_range, uint64_t start, uint64_t end, const uint32_t *cols, uint64_t n_cols,
+                              uint8_t *out, uint64_t out_cap, uint64_t *out_len) {
+    if (!c || (!in && n) || (!ref && ref_len) || (!out && out_cap) || !out_len) return VCFC_E_ARG;
+    *out_len = 0;
+    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
+    SubsetCall sc;
+    int st = sc.prepare(in, n, cols, n_cols);
+    if (st) return st;
+    uint64_t o = 0;
+    bool fits = true;
+    auto sink = [&](const uint8_t *p, uint64_t k) {
+        if (fits && o + k <= out_cap) memcpy(out + o, p, k);
+        else fits = false;
+        o += k;
+        return true;
+    };
+    CtxDecodeBuffers B(c);
+    st = vcfc_sub::query_section(in + sc.data_off, n - sc.data_off, sc.S, sc.csort, sc.rank,
+                                 reinterpret_cast<const uint8_t *>(ref), ref_len, has_range, start, end, B, c->stream,
+                                 sink);
+    *out_len = o;
+    if (!fits) return VCFC_E_NOSPACE;
+    return st;
+}
+
+int vcfc_query_samples_file(vcfc_ctx *c, const char *in_path, const char *ref, uint64_t ref_len, int has_range,
+                            uint64_t start, uint64_t end, const uint32_t *cols, uint64_t n_cols, int out_fd) {
+    if (!c || !in_path || (!ref && ref_len) || out_fd < 0) return VCFC_E_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
+    MappedFile f;
+    int st = f.open_ro(in_path);
+    if (st) return st;
+    SubsetCall sc;
+    if ((st = sc.prepare(f.p, f.n, cols, n_cols))) return st;
+    auto sink = [&](const uint8_t *p, uint64_t k) {
+        while (k) {
+            const ssize_t w = write(out_fd, p, std::min<uint64_t>(k, 1ull << 30));
+            if (w <= 0) return false;
+            p += w;
+            k -= (uint64_t)w;
+        }
+        return true;
+    };
+    CtxDecodeBuffers B(c);
+    return vcfc_sub::query_section(f.p + sc.data_off, f.n - sc.data_off, sc.S, sc.csort, sc.rank,
+                                   reinterpret_cast<const uint8_t *>(ref), ref_len, has_range, start, end, B, c->stream,
+                                   sink);
+}
+
+uint64_t vcfc_subset_workspace_size(uint64_t n_records, uint64_t n_cols) {
+    return vcfc_subset_workspace_layout(n_records, n_cols).total;
+}
+
+int vcfc_decode_samples_device(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_rec_start,
+                               const uint8_t *d_select, uint64_t n, uint64_t samples, const uint32_t *cols,
+                               uint64_t n_cols, uint8_t *d_out, uint64_t out_cap, uint64_t *d_line_off, void *d_ws,
+                               uint64_t ws_bytes, uint64_t *d_err, void *stream) {
+    if ((n && (!d_in || !d_rec_start || !d_out)) || !d_ws || !d_line_off || !d_err) return VCFC_E_ARG;
+    std::vector<uint32_t> csort, rank;
+    if (vcfc_sub::sort_columns(cols, n_cols, samples, csort, rank)) return VCFC_E_ARG;
+    const VcfcSubsetLayout L = vcfc_subset_workspace_layout(n, n_cols);
+    if (ws_bytes < L.total) return VCFC_E_NOSPACE;
+    uint8_t *ws = static_cast<uint8_t *>(d_ws);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    VcfcSubsetArgs a;
+    a.in = d_in; a.n_bytes = in_bytes; a.rec_start = d_rec_start; a.select = d_select; a.n = n; a.S = samples;
+    a.K = (uint32_t)n_cols; a.out = d_out; a.out_cap = out_cap; a.line_off = d_line_off;
+    vcfc_subset_args_workspace(a, ws, L);
+    a.err = d_err;
+    // csort and rank live on this frame: the stream has taken them when the synchronise returns
+    if (hipMemcpyAsync(ws + L.csort, csort.data(), 4 * n_cols, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(ws + L.rank, rank.data(), 4 * n_cols, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return VCFC_E_HIP;
+    if (vcfc_subset_plan(a, s) != hipSuccess) return VCFC_E_HIP;
+    return vcfc_subset_write(a, 0, n, s) == hipSuccess ? VCFC_OK : VCFC_E_HIP;
 }
 
 int vcfc_query_match_device(const uint8_t *d_in, const uint64_t *d_rec_start, uint64_t n, const uint8_t *d_ref,

@@ -229,6 +229,56 @@ hipError_t vcfc_scan_u32(const uint32_t *in, uint64_t n, uint64_t *partials, uin
 hipError_t vcfc_scan_kinds(const uint32_t *in, uint64_t n, uint64_t *partials, uint64_t *out, hipStream_t s);
 
 // ---------------------------------------------------------------------------
+// Sample-subset decoder (vcfc_subset.hip): REQ and K chosen
+// sample columns of every record.  A record that is not regular (DESIGN.md
+// §4i) gets no line and is reported in err.
+struct VcfcSubsetArgs {
+    const uint8_t *in;          // data section bytes (device)
+    uint64_t n_bytes;
+    const uint64_t *rec_start;  // n + 1 record offsets into `in`
+    const uint8_t *select;      // nullptr, or per record: 0 = skip it (no line, not checked)
+    uint64_t n;                 // records
+    uint64_t S;                 // samples declared by the header line (1 <= S < 2^31)
+    const uint32_t *csort;      // the K chosen columns, ascending (distinct, < S)
+    const uint32_t *rank;       // rank[k]: output slot of column csort[k]
+    uint32_t K;                 // 1 <= K <= S
+    uint8_t *out;               // lines, concatenated
+    uint64_t out_cap;
+    uint64_t *line_off;         // n + 1 exclusive offsets of the lines in `out`
+    // workspace (vcfc_subset_workspace_layout)
+    uint32_t *st;               // per-record plan status
+    uint32_t *line_size;        // per-record line bytes
+    uint32_t *seq_list;         // records left to the byte-serial path
+    uint32_t *seq_count;
+    uint64_t *err;              // min over records of (i << 8 | code): 3 = not regular, 0xFF = out_cap short
+    uint64_t *partials;         // scan partials
+    uint32_t *seq_scratch;      // VCFC_SUBSET_SEQ_LANES * K words: token offsets of the byte-serial writer
+};
+// lanes of the byte-serial writer (each owns K words of seq_scratch)
+#define VCFC_SUBSET_SEQ_LANES 1024u
+
+struct VcfcSubsetLayout {
+    uint64_t st, line_size, seq_list, seq_count, err, partials, csort, rank, seq_scratch, total;
+};
+VcfcSubsetLayout vcfc_subset_workspace_layout(uint64_t n, uint64_t K);
+// Point a's workspace arrays into ws (err, csort and rank included).
+inline void vcfc_subset_args_workspace(VcfcSubsetArgs &a, uint8_t *ws, const VcfcSubsetLayout &L) {
+    a.st = reinterpret_cast<uint32_t *>(ws + L.st);
+    a.line_size = reinterpret_cast<uint32_t *>(ws + L.line_size);
+    a.seq_list = reinterpret_cast<uint32_t *>(ws + L.seq_list);
+    a.seq_count = reinterpret_cast<uint32_t *>(ws + L.seq_count);
+    a.err = reinterpret_cast<uint64_t *>(ws + L.err);
+    a.partials = reinterpret_cast<uint64_t *>(ws + L.partials);
+    a.csort = reinterpret_cast<uint32_t *>(ws + L.csort);
+    a.rank = reinterpret_cast<uint32_t *>(ws + L.rank);
+    a.seq_scratch = reinterpret_cast<uint32_t *>(ws + L.seq_scratch);
+}
+// exact plan: statuses, line sizes, line offsets, err (no host synchronisation)
+hipError_t vcfc_subset_plan(const VcfcSubsetArgs &a, hipStream_t s);
+// write lines [first, last) at a.out + line_off[i] (after vcfc_subset_plan)
+hipError_t vcfc_subset_write(const VcfcSubsetArgs &a, uint64_t first, uint64_t last, hipStream_t s);
+
+// ---------------------------------------------------------------------------
 // Range query (vcfc_decode.hip; reference query_compressed_file,
 // src/main.cpp:3777-3929).  `ref` is device memory.
 struct VcfcQuery {

@@ -1,0 +1,222 @@
+// vcfc_subset_driver.h -- host driver of the sample-subset decoder
+// (DESIGN.md §4i), shared by the C ABI (vcfc_api.cpp) and the CPU emulator
+// harness (tests/simt_emu/emu_subset_api.cpp), so the same control flow is
+// tested on both.
+//
+//   1. the header: '##' lines verbatim, the '#CHROM' line cut to its first 9
+//      fields and the chosen names;
+//   2. hop the LEN headers on the host to find record starts;
+//   3. plan every record on the GPU exactly (line sizes, first irregular one);
+//   4. write the lines before it in output batches;
+//   5. VCFC_E_FORMAT at the first record that is not regular, or where
+//      hopping stopped with 8 or more bytes left.
+// The query variant runs the range query's match step first (its kernel and
+// error word unchanged) and decodes the matching records only.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+#include <numeric>
+#include <vector>
+
+#include "vcfc_decode_driver.h"
+#include "vcfc_device.h"
+
+namespace vcfc_sub {
+
+using vcfc_dec::Buffers;
+using vcfc_dec::Sink;
+constexpr int ST_OK = 0, ST_E_ARG = 5, ST_E_HIP = 6, ST_E_IO = 7, ST_E_FORMAT = 8;   // = include/vcfc.h codes
+
+// The chosen columns, ascending, and each one's output slot.  ST_E_ARG: no
+// column, a column >= S, a column listed twice.
+inline int sort_columns(const uint32_t *cols, uint64_t K, uint64_t S, std::vector<uint32_t> &csort,
+                        std::vector<uint32_t> &rank) {
+    if (!cols || K == 0 || K > S || S >= (1ull << 31)) return ST_E_ARG;
+    rank.resize(K);
+    std::iota(rank.begin(), rank.end(), 0u);
+    std::sort(rank.begin(), rank.end(), [&](uint32_t x, uint32_t y) { return cols[x] < cols[y]; });
+    csort.resize(K);
+    for (uint64_t k = 0; k < K; k++) csort[k] = cols[rank[k]];
+    if (csort[K - 1] >= S) return ST_E_ARG;
+    for (uint64_t k = 1; k < K; k++)
+        if (csort[k] == csort[k - 1]) return ST_E_ARG;
+    return ST_OK;
+}
+
+// The fields of the '#CHROM' line of a header parse_header accepts:
+// f[j] = offset of field j, f.back() = the line's LF + 1 (= data_off).
+inline void header_fields(const uint8_t *in, uint64_t data_off, std::vector<uint64_t> &f) {
+    uint64_t ls = data_off - 1;   // the line's LF
+    while (ls > 0 && in[ls - 1] != '\n') ls--;
+    f.clear();
+    f.push_back(ls);
+    for (uint64_t k = ls; k + 1 < data_off; k++)
+        if (in[k] == '\t') f.push_back(k + 1);
+    f.push_back(data_off);
+}
+
+// The subset's header.  ST_E_FORMAT where parse_header fails, ST_E_ARG for a
+// column >= S (sort_columns checks the rest).
+inline int subset_header(const uint8_t *in, uint64_t n, const uint32_t *cols, uint64_t K, std::vector<uint8_t> &hdr,
+                         uint64_t *data_off, uint64_t *S) {
+    int st = vcfc_dec::parse_header(in, n, data_off, S);
+    if (st) return st;
+    if (!cols || K == 0) return ST_E_ARG;
+    for (uint64_t k = 0; k < K; k++)
+        if (cols[k] >= *S) return ST_E_ARG;
+    std::vector<uint64_t> f;
+    header_fields(in, *data_off, f);   // S + 9 fields
+    hdr.assign(in, in + f[9] - 1);     // through the 9th field, without its TAB
+    for (uint64_t k = 0; k < K; k++) {
+        hdr.push_back('\t');
+        hdr.insert(hdr.end(), in + f[9 + cols[k]], in + f[10 + cols[k]] - 1);
+    }
+    hdr.push_back('\n');
+    return ST_OK;
+}
+
+// The lines of the records [rec[i], rec[i + 1]), i < nrec, of the uploaded
+// data section (d_select, nullable: records with select[i] == 0 get no line
+// and are not checked), sunk in order.  *stop = 1: a record is not regular;
+// the lines before it are sunk.
+inline int subset_records(const uint8_t *d_in, uint64_t n, uint64_t S, const uint64_t *d_rec, const uint8_t *d_select,
+                          uint64_t nrec, const std::vector<uint32_t> &csort, const std::vector<uint32_t> &rank,
+                          Buffers &B, hipStream_t s, const Sink &sink, uint64_t out_batch, int *stop) {
+    *stop = 0;
+    if (!nrec) return ST_OK;
+    const uint64_t K = csort.size();
+    const VcfcSubsetLayout L = vcfc_subset_workspace_layout(nrec, K);
+    uint8_t *ws = static_cast<uint8_t *>(B.get(Buffers::WS, L.total));
+    uint64_t *d_loff = static_cast<uint64_t *>(B.get(Buffers::LINE_OFF, 8 * (nrec + 1)));
+    if (!ws || !d_loff) return ST_E_HIP;
+    VcfcSubsetArgs a;
+    a.in = d_in; a.n_bytes = n; a.rec_start = d_rec; a.select = d_select; a.n = nrec; a.S = S; a.K = (uint32_t)K;
+    a.out = nullptr; a.out_cap = 0; a.line_off = d_loff;
+    vcfc_subset_args_workspace(a, ws, L);
+    if (hipMemcpyAsync(ws + L.csort, csort.data(), 4 * K, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(ws + L.rank, rank.data(), 4 * K, hipMemcpyHostToDevice, s) != hipSuccess)
+        return ST_E_HIP;
+    uint64_t err = 0;
+    if (vcfc_subset_plan(a, s) != hipSuccess || hipMemcpyAsync(&err, a.err, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return ST_E_HIP;
+    uint64_t n_lines = nrec;
+    if (err != VCFCD_NO_ERROR) {
+        n_lines = err >> 8;
+        *stop = 1;
+    }
+    std::vector<uint64_t> loff(n_lines + 1);
+    if (hipMemcpyAsync(loff.data(), d_loff, 8 * (n_lines + 1), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return ST_E_HIP;
+    for (uint64_t i0 = 0; i0 < n_lines;) {
+        uint64_t i1 = i0 + 1;
+        while (i1 < n_lines && loff[i1 + 1] - loff[i0] <= out_batch) i1++;
+        const uint64_t bytes = loff[i1] - loff[i0];
+        if (bytes) {
+            uint8_t *d_out = static_cast<uint8_t *>(B.get(Buffers::OUT, bytes + 64));
+            uint8_t *host = B.host(Buffers::HOST_OUT, bytes + 64);
+            if (!d_out || !host) return ST_E_HIP;
+            a.out = d_out - loff[i0];   // lines are written at out + line_off[i]
+            a.out_cap = loff[i1];
+            if (vcfc_subset_write(a, i0, i1, s) != hipSuccess ||
+                hipMemcpyAsync(host, d_out, bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                hipStreamSynchronize(s) != hipSuccess)
+                return ST_E_HIP;
+            if (!sink(host, bytes)) return ST_E_IO;
+        }
+        i0 = i1;
+    }
+    return ST_OK;
+}
+
+// The data section of a .vcfc (host bytes h_in[0, n); uploaded here).
+inline int decode_section(const uint8_t *h_in, uint64_t n, uint64_t S, const std::vector<uint32_t> &csort,
+                          const std::vector<uint32_t> &rank, Buffers &B, hipStream_t s, const Sink &sink,
+                          uint64_t out_batch = 1ull << 30) {
+    std::vector<uint64_t> rec;
+    vcfc_dec::hop(h_in, n, rec);
+    const uint64_t nrec = rec.size() - 1;
+    if (nrec) {
+        const uint8_t *d_in = vcfc_dec::upload(B, Buffers::IN, h_in, n, s);
+        const uint64_t *d_rec = reinterpret_cast<const uint64_t *>(
+            vcfc_dec::upload(B, Buffers::REC, reinterpret_cast<const uint8_t *>(rec.data()), 8 * rec.size(), s));
+        if (!d_in || !d_rec) return ST_E_HIP;
+        int stop = 0;
+        const int st = subset_records(d_in, n, S, d_rec, nullptr, nrec, csort, rank, B, s, sink, out_batch, &stop);
+        if (st) return st;
+        if (stop) return ST_E_FORMAT;
+    }
+    return n - rec.back() >= 8 ? ST_E_FORMAT : ST_OK;   // fewer than 8 bytes left: a clean end
+}
+
+// The matching records' lines (no header): matched exactly as
+// vcfc_dec::query_section matches them; only matching records must be
+// regular.  A match error at record k stops there.
+inline int query_section(const uint8_t *h_in, uint64_t n, uint64_t S, const std::vector<uint32_t> &csort,
+                         const std::vector<uint32_t> &rank, const uint8_t *qref, uint64_t qref_len, int has_range,
+                         uint64_t qstart, uint64_t qend, Buffers &B, hipStream_t s, const Sink &sink,
+                         uint64_t out_batch = 1ull << 30) {
+    if (qref_len > 0xFFFFFFFFull) return ST_E_FORMAT;
+    std::vector<uint64_t> rec;
+    vcfc_dec::hop(h_in, n, rec);
+    const uint64_t nrec = rec.size() - 1;
+    if (nrec) {
+        const uint8_t *d_in = vcfc_dec::upload(B, Buffers::IN, h_in, n, s);
+        const uint8_t *d_ref = vcfc_dec::upload(B, Buffers::QREF, qref, qref_len, s);
+        uint64_t *d_small = static_cast<uint64_t *>(B.get(Buffers::SMALL, 64));
+        const uint64_t *d_rec = reinterpret_cast<const uint64_t *>(
+            vcfc_dec::upload(B, Buffers::REC, reinterpret_cast<const uint8_t *>(rec.data()), 8 * rec.size(), s));
+        uint8_t *d_flag = static_cast<uint8_t *>(B.get(Buffers::FLAG, nrec + 64));
+        if (!d_in || !d_ref || !d_small || !d_rec || !d_flag) return ST_E_HIP;
+        VcfcQuery q;
+        q.ref = d_ref; q.ref_len = (uint32_t)qref_len; q.has_range = has_range ? 1u : 0u; q.start = qstart; q.end = qend;
+        uint64_t err = 0;
+        if (vcfc_query_match(d_in, d_rec, nrec, q, d_flag, d_small, s) != hipSuccess ||
+            hipMemcpyAsync(&err, d_small, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+            return ST_E_HIP;
+        const uint64_t k = err == VCFCD_NO_ERROR ? nrec : err >> 8;   // the first record with a match error
+        int stop = 0;
+        const int st = subset_records(d_in, n, S, d_rec, d_flag, k, csort, rank, B, s, sink, out_batch, &stop);
+        if (st) return st;
+        if (stop || k < nrec) return ST_E_FORMAT;
+    }
+    return n - rec.back() >= 8 ? ST_E_FORMAT : ST_OK;
+}
+
+// Resolve a comma-separated name list against the '#CHROM' line (the first
+// occurrence wins where the header repeats a name).  ST_E_ARG with *bad_off =
+// the offset in `names` of a name the header lacks, or of a name's second
+// listing; 4 (VCFC_E_NOSPACE) with *n_cols set where cols_cap is short.
+inline int sample_columns(const uint8_t *in, uint64_t n, const char *names, uint64_t names_len, uint32_t *cols,
+                          uint64_t cols_cap, uint64_t *n_cols, uint64_t *bad_off) {
+    uint64_t data_off = 0, S = 0;
+    const int st = vcfc_dec::parse_header(in, n, &data_off, &S);
+    if (st) return st;
+    std::vector<uint64_t> f;
+    header_fields(in, data_off, f);
+    std::vector<uint32_t> got;
+    for (uint64_t a = 0;;) {
+        uint64_t b = a;
+        while (b < names_len && names[b] != ',') b++;
+        uint64_t col = S;
+        for (uint64_t j = 0; j < S && col == S; j++) {
+            const uint64_t f0 = f[9 + j], f1 = f[10 + j] - 1;
+            if (f1 - f0 == b - a && memcmp(in + f0, names + a, b - a) == 0) col = j;
+        }
+        if (col == S || std::find(got.begin(), got.end(), (uint32_t)col) != got.end()) {
+            *bad_off = a;
+            return ST_E_ARG;
+        }
+        got.push_back((uint32_t)col);
+        if (b >= names_len) break;
+        a = b + 1;
+    }
+    *n_cols = got.size();
+    if (got.size() > cols_cap) return 4;
+    std::copy(got.begin(), got.end(), cols);
+    return ST_OK;
+}
+
+}  // namespace vcfc_sub

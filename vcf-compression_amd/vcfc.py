@@ -50,6 +50,9 @@ EXPORTS = [
     "vcfc_sparse_index_workspace_size", "vcfc_sparse_index_offset", "vcfc_sparse_index_device",
     "vcfc_create_sparse_index_file", "vcfc_query_sparse_index_file",
     "vcfc_decode_sizes_workspace_size", "vcfc_decode_sizes_device", "vcfc_gap_analysis_file",
+    "vcfc_sample_columns", "vcfc_subset_workspace_size", "vcfc_decode_samples_device",
+    "vcfc_decompress_samples_buffer", "vcfc_decompress_samples_file",
+    "vcfc_query_samples_buffer", "vcfc_query_samples_file",
 ]
 LINE_INDEX_HOP, LINE_INDEX_SCAN = 0, 1                       # include/vcfc.h VCFC_LINE_INDEX_*
 TRACE_INGEST, TRACE_DEVICE, TRACE_SPARSE_QUERY = 1, 2, 4     # include/vcfc.h VCFC_TRACE_*
@@ -110,12 +113,22 @@ def lib():
                                              u64, u64, ctypes.c_int],
             "vcfc_decode_sizes_workspace_size": [u64],
             "vcfc_decode_sizes_device": [vp, u64, vp, u64, u64, vp, vp, vp, vp, vp, u64, vp, vp],
-            "vcfc_gap_analysis_file": [vp, ctypes.c_char_p, ctypes.c_char_p]}
+            "vcfc_gap_analysis_file": [vp, ctypes.c_char_p, ctypes.c_char_p],
+            # the sample subset
+            "vcfc_sample_columns": [vp, u64, ctypes.c_char_p, u64, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(u64)],
+            "vcfc_subset_workspace_size": [u64, u64],
+            "vcfc_decode_samples_device": [vp, u64, vp, vp, u64, u64, vp, u64, vp, u64, vp, vp, u64, vp, vp],
+            "vcfc_decompress_samples_buffer": [vp, vp, u64, vp, u64, vp, u64, ctypes.POINTER(u64)],
+            "vcfc_decompress_samples_file": [vp, ctypes.c_char_p, ctypes.c_char_p, vp, u64],
+            "vcfc_query_samples_buffer": [vp, vp, u64, ctypes.c_char_p, u64, ctypes.c_int, u64, u64, vp, u64, vp, u64,
+                                          ctypes.POINTER(u64)],
+            "vcfc_query_samples_file": [vp, ctypes.c_char_p, ctypes.c_char_p, u64, ctypes.c_int, u64, u64, vp, u64,
+                                        ctypes.c_int]}
     for name, args in late.items():
         if hasattr(L, name):
             getattr(L, name).argtypes = args
     for name in ("vcfc_index_workspace_size", "vcfc_sparse_index_workspace_size", "vcfc_sparse_index_offset",
-                 "vcfc_decode_sizes_workspace_size"):
+                 "vcfc_decode_sizes_workspace_size", "vcfc_subset_workspace_size"):
         if hasattr(L, name):
             getattr(L, name).restype = u64
     L.vcfc_record_hash_device.argtypes = [vp, vp, u64, vp, vp]
@@ -458,6 +471,60 @@ class Context:
         raise_for(lib().vcfc_query_file(self._h, in_path.encode(), query.reference_name, len(query.reference_name),
                                         int(query.has_range), query.start, query.end, out_fd))
 
+    def decompress_samples_buffer(self, data, cols, cap=None):
+        """decompress-samples: the header and every line cut
+        to the 0-based sample columns `cols`, in that order.  Returns (status,
+        bytes): on VCFC_E_FORMAT the bytes are the header and the lines before
+        the first record that is not regular; VCFC_E_ARG (no column, a column
+        past the header's samples, a column listed twice) writes nothing."""
+        src = np.frombuffer(data, dtype=np.uint8)
+        c = np.asarray(cols, dtype=np.uint32)
+        cap = cap if cap is not None else len(data) + 16 * len(c) * (len(data) // 64 + 1) + 4096
+        while True:
+            out = np.empty(max(cap, 1), dtype=np.uint8)
+            n = ctypes.c_uint64(0)
+            st = _need("vcfc_decompress_samples_buffer")(self._h, src.ctypes.data, len(data), c.ctypes.data, len(c),
+                                                         out.ctypes.data, cap, ctypes.byref(n))
+            if st == E_NOSPACE and n.value > cap:
+                cap = n.value
+                continue
+            return st, out[:n.value].tobytes()
+
+    def decompress_samples_file(self, in_path, out_path, cols):
+        c = np.asarray(cols, dtype=np.uint32)
+        raise_for(_need("vcfc_decompress_samples_file")(self._h, in_path.encode(), out_path.encode(), c.ctypes.data,
+                                                        len(c)))
+
+    def query_samples_buffer(self, data, query, cols, cap=None):
+        """query-samples: the matching lines (no header) cut to `cols`.
+        Records match as in query_buffer; only matching records must be
+        regular.  Returns (status, bytes)."""
+        if not isinstance(query, VcfCoordinateQuery):
+            query = parse_coordinate_string(query)
+        src = np.frombuffer(data, dtype=np.uint8)
+        c = np.asarray(cols, dtype=np.uint32)
+        cap = cap if cap is not None else len(data) + 16 * len(c) * (len(data) // 64 + 1) + 4096
+        while True:
+            out = np.empty(max(cap, 1), dtype=np.uint8)
+            n = ctypes.c_uint64(0)
+            st = _need("vcfc_query_samples_buffer")(self._h, src.ctypes.data, len(data), query.reference_name,
+                                                    len(query.reference_name), int(query.has_range), query.start,
+                                                    query.end, c.ctypes.data, len(c), out.ctypes.data, cap,
+                                                    ctypes.byref(n))
+            if st == E_NOSPACE and n.value > cap:
+                cap = n.value
+                continue
+            return st, out[:n.value].tobytes()
+
+    def query_samples_file(self, in_path, query, cols, out_fd=1):
+        """As `main query-samples <file> <query> <names>`, with columns."""
+        if not isinstance(query, VcfCoordinateQuery):
+            query = parse_coordinate_string(query)
+        c = np.asarray(cols, dtype=np.uint32)
+        raise_for(_need("vcfc_query_samples_file")(self._h, in_path.encode(), query.reference_name,
+                                                   len(query.reference_name), int(query.has_range), query.start,
+                                                   query.end, c.ctypes.data, len(c), out_fd))
+
     def sparse_query_status(self, in_path, query):
         """query_sparse_file_fd (reference src/main.cpp:235-582) over a sparse
         file: (status, stdout bytes); E_FORMAT where the reference throws (the
@@ -759,3 +826,39 @@ def binned_index_device(d_in, d_rec_start, n, base_offset, entries_per_bin, d_en
 def record_span_device(d_in, d_rec_start, n, d_ref_idx, d_pos, d_end, d_err, stream=0):
     """Per record ref_idx (u8), POS and end position (u64 each) on the GPU."""
     raise_for(_need("vcfc_record_span_device")(d_in, d_rec_start, n, d_ref_idx, d_pos, d_end, d_err, stream))
+
+
+def sample_columns(data, names):
+    """The 0-based sample columns of `names` (a list of names, or one
+    comma-separated string) in the '#CHROM' line of .vcfc bytes (the header
+    is enough), in list order.  Raises ValueError for a name the header does
+    not hold or a name listed twice."""
+    nb = names if isinstance(names, (bytes, str)) else b",".join(x.encode() if isinstance(x, str) else x for x in names)
+    nb = nb.encode() if isinstance(nb, str) else bytes(nb)
+    src = np.frombuffer(data, dtype=np.uint8)
+    cap = nb.count(b",") + 1
+    cols = np.zeros(cap, dtype=np.uint32)
+    n, bad = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    st = _need("vcfc_sample_columns")(src.ctypes.data, len(data), nb, len(nb), cols.ctypes.data, cap, ctypes.byref(n),
+                                      ctypes.byref(bad))
+    if st == E_ARG:
+        name = nb[bad.value:].split(b",")[0]
+        kind = "Duplicate" if name in nb[:bad.value].split(b",")[:-1] else "Unknown"
+        raise ValueError("%s sample name: %s" % (kind, name.decode(errors="replace")))
+    raise_for(st)
+    return [int(x) for x in cols[:n.value]]
+
+
+def subset_workspace_size(n_records, n_cols):
+    return int(_need("vcfc_subset_workspace_size")(n_records, n_cols))
+
+
+def decode_samples_device(d_in, in_bytes, d_rec_start, d_select, n, samples, cols, d_out, out_cap, d_line_off, d_ws,
+                          ws_bytes, d_err, stream=0):
+    """The lines of device-resident records cut to the sample columns `cols`
+    (host list; include/vcfc.h vcfc_decode_samples_device); d_select may be
+    None.  Returns the status (VCFC_E_ARG for bad columns); enqueued on
+    `stream`."""
+    c = np.asarray(cols, dtype=np.uint32)
+    return _need("vcfc_decode_samples_device")(d_in, in_bytes, d_rec_start, d_select, n, samples, c.ctypes.data, len(c),
+                                               d_out, out_cap, d_line_off, d_ws, ws_bytes, d_err, stream)
