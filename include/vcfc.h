@@ -485,6 +485,75 @@ int vcfc_decode_samples_device(const uint8_t *d_in, uint64_t in_bytes, const uin
                                uint64_t n_cols, uint8_t *d_out, uint64_t out_cap, uint64_t *d_line_off, void *d_ws,
                                uint64_t ws_bytes, uint64_t *d_err, void *stream);
 
+/* ---- genotype counts: genotype-counts (no reference action:
+ * the oracle is a tally over the reference's own decode) ---------------------
+ * Counts taken from the run-length code without decoding it.  S is the
+ * '#CHROM' line's sample count; S == 0 or S >= 2^30 is VCFC_E_ARG and a
+ * header the decoder refuses VCFC_E_FORMAT, both with nothing written.
+ * Records are found by LEN hops.  Without a query every record is counted,
+ * and the call stops with VCFC_E_FORMAT at the first record that is not
+ * regular (as defined above for the sample subset), or where hopping stops
+ * with 8 or more bytes left.  With a query, records are matched exactly as
+ * vcfc_query_buffer matches them; only matching records are counted and need
+ * to be regular; a match error at record k stops there with VCFC_E_FORMAT.
+ *
+ * Per counted record, one row of eight uint32:
+ *   n00 n01 n10 n11 n_other AN AC1 AC_other
+ * n00 .. n11: the tokens that are exactly 0|0, 0|1, 1|0, 1|1 (run bytes by
+ * class, and any escaped token that spells one of the four); n_other: every
+ * other token; the five add up to S.  AN / AC1 / AC_other come from each
+ * token's GT subfield under one total rule: GT is the token up to its first
+ * ':' (or the whole token); it is split at every '|' and '/' (an empty GT is
+ * one empty piece); a piece of one or more ASCII digits is a called allele of
+ * class v = min(2, 10 v + d) folded over its digits from 0 (0, 00 -> 0; 1, 01
+ * -> 1; 2, 10, 010 -> 2); every other piece is missing and counted nowhere.
+ * AN = called alleles, AC1 = those of class 1, AC_other = those of class 2.
+ * With S < 2^30 and records below 2^31 bytes nothing overflows 32 bits.
+ * Per sample j < S, five uint64 c00 c01 c10 c11 c_other: the counted records
+ * whose token j falls in each class.
+ *
+ * Device entry: the records d_in[d_rec_start[i], d_rec_start[i+1]), i < n <
+ * 2^32 (d_select nullable: records with d_select[i] == 0 get a zero row and
+ * are neither counted nor checked), read once.  d_variant (nullable, 16-byte
+ * aligned): 8 n uint32, row i for record i.  d_sample (nullable): 5 samples
+ * uint64, sample-major, ADDED to: the caller zeroes it, so batches and files
+ * accumulate.  Asynchronous on `stream`, no host synchronisation.  *d_err =
+ * ~0, or the minimum over records of (i << 8 | 3) where a record is not
+ * regular: rows from record i on and the whole sample table are then not
+ * meaningful.  VCFC_E_ARG: both outputs null, samples == 0 or >= 2^30, n >=
+ * 2^32, ws_bytes below vcfc_counts_workspace_size(n, samples).  As in the
+ * decoder, up to 3 bytes past the last record's end
+ * must be readable.  vcfc_counts_lds_samples(): the largest `samples` whose
+ * histogram is summed in LDS (above it the general path takes global
+ * atomics). */
+uint64_t vcfc_counts_workspace_size(uint64_t n_records, uint64_t samples);
+uint64_t vcfc_counts_lds_samples(void);
+int vcfc_genotype_counts_device(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_rec_start,
+                                const uint8_t *d_select, uint64_t n, uint64_t samples, uint32_t *d_variant,
+                                uint64_t *d_sample, void *d_ws, uint64_t ws_bytes, uint64_t *d_err, void *stream);
+/* A whole .vcfc in host memory.  has_query == 0: every record (ref .. end are
+ * ignored).  rec_index[0, *n_rows) = the counted records' file indices and
+ * rows[8 r ..] their rows: VCFC_E_NOSPACE if rows_cap is short (*n_rows =
+ * rows needed).  sample_table: 5 S uint64, VCFC_E_NOSPACE if sample_cap (in
+ * samples) is below S (*n_samples = S).  On VCFC_E_FORMAT the rows before the
+ * failing record are returned, *err_record is its file index (the record
+ * count where hopping stopped short) and the sample table is not written. */
+int vcfc_genotype_counts_buffer(vcfc_ctx *ctx, const uint8_t *in, uint64_t in_bytes, int has_query, const char *ref,
+                                uint64_t ref_len, int has_range, uint64_t start, uint64_t end, uint64_t *rec_index,
+                                uint32_t *rows, uint64_t rows_cap, uint64_t *n_rows, uint64_t *sample_table,
+                                uint64_t sample_cap, uint64_t *n_samples, uint64_t *err_record);
+/* Both outputs are opened (created, truncated) before the input is parsed.
+ * variants_tsv: "#CHROM\tPOS\tN_00\tN_01\tN_10\tN_11\tN_OTHER\tAN\tAC1\t
+ * AC_OTHER\n", then per counted record REQ's first two TAB fields verbatim
+ * and the eight numbers in decimal, TAB-separated.  samples_tsv:
+ * "#SAMPLE\tN_00\tN_01\tN_10\tN_11\tN_OTHER\n", then per sample its name
+ * verbatim from the '#CHROM' line and the five numbers.  On VCFC_E_FORMAT
+ * past the header the variants file holds its header line and the lines
+ * before the failing record, and the samples file stays empty. */
+int vcfc_genotype_counts_file(vcfc_ctx *ctx, const char *in_vcfc, const char *variants_tsv, const char *samples_tsv,
+                              int has_query, const char *ref, uint64_t ref_len, int has_range, uint64_t start,
+                              uint64_t end);
+
 /* ---- sparse layout: sparsify_file (reference src/sparse.cpp:290-580) -------
  * Record i of the .vcfc goes to data_start + (300e6 + POS_i) * 16384
  * (compute_sparse_offset, src/sparse.cpp:18-51) behind a 16-byte prefix

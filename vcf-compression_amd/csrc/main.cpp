@@ -6,7 +6,9 @@
 // `main create-sparse-index <in>` and `main query-sparse-index <in> <region>`,
 // and `main gap-analysis <in>`; beyond the reference, the sample subset:
 // `main decompress-samples <in> <out> <names>` and
-// `main query-samples <in> <query> <names>`.  Data lines are
+// `main query-samples <in> <query> <names>`, and the counts:
+// `main genotype-counts <in> <variants.tsv> <samples.tsv> [<query>]`
+// (DESIGN.md §4j).  Data lines are
 // encoded on the GPU through libvcfc.so.  Error messages mirror the
 // reference's exceptions (which terminate the reference process).
 #include <cerrno>
@@ -31,7 +33,8 @@ static int usage() {
                     "./main query-sparse-index <compressed-filename> <region>\n"
                     "./main gap-analysis <compressed-filename>\n"
                     "./main decompress-samples <input_file> <output_file> <name>[,<name>...]\n"
-                    "./main query-samples <input_file> <ref>[:<start>-<end>] <name>[,<name>...]\n");
+                    "./main query-samples <input_file> <ref>[:<start>-<end>] <name>[,<name>...]\n"
+                    "./main genotype-counts <input_file> <variants.tsv> <samples.tsv> [<ref>[:<start>-<end>]]\n");
     return 1;
 }
 
@@ -451,6 +454,50 @@ int main(int argc, char **argv) {
         }
         if (st != VCFC_OK) {
             fprintf(stderr, "Error in decompression of file: %s\n", vcfc_strerror(st));
+            return 1;
+        }
+        return 0;
+    }
+    if (action == "genotype-counts") {
+        // no reference counterpart: per-variant and per-sample genotype counts as two TSV files
+        if (argc < 5) return usage();
+        if (!file_exists(argv[2])) printf("Input file does not exist: %s\n", argv[2]);
+        if (std::string(argv[2]) == argv[3] || std::string(argv[2]) == argv[4] || std::string(argv[3]) == argv[4]) {
+            fprintf(stderr, "terminate called after throwing an instance of 'std::runtime_error'\n"
+                            "  what():  input and output file are the same\n");
+            return 134;
+        }
+        const bool query = argc > 5;
+        const std::string q(query ? argv[5] : "");
+        uint64_t ref_len = 0, start = 0, end = 0;
+        int has_range = 0;
+        if (query) {
+            const int pq = vcfc_parse_query(q.data(), q.size(), &ref_len, &has_range, &start, &end);
+            if (pq != 0) {
+                const size_t colon = q.find(':'), dash = q.find('-', colon + 1);
+                if (pq == 1) printf("Query must contain a dash character: <ref>:<start>-<end>\n");
+                else if (pq == 2) printf("Failed to parse int from start position: %s\n", q.substr(colon + 1, dash - colon - 1).c_str());
+                else printf("Failed to parse int from end position: %s\n", q.substr(dash + 1).c_str());
+                printf("Failed to parse query string: %s\n", q.c_str());
+                return 1;
+            }
+        }
+        vcfc_ctx *ctx = nullptr;
+        int st = vcfc_ctx_create(0, &ctx);
+        if (st != VCFC_OK) {
+            fprintf(stderr, "vcfc: %s\n", vcfc_strerror(st));
+            return 1;
+        }
+        fflush(stdout);
+        st = vcfc_genotype_counts_file(ctx, argv[2], argv[3], argv[4], query ? 1 : 0, q.data(), ref_len, has_range, start, end);
+        vcfc_ctx_destroy(ctx);
+        if (st == VCFC_E_FORMAT) {
+            fprintf(stderr, "terminate called after throwing an instance of 'VcfValidationError'\n"
+                            "  what():  %s\n", vcfc_strerror(st));
+            return 134;
+        }
+        if (st != VCFC_OK) {
+            fprintf(stderr, "Error in genotype-counts of file: %s\n", vcfc_strerror(st));
             return 1;
         }
         return 0;

@@ -24,6 +24,7 @@
 #include "vcfc_ingest_driver.h"
 #include "vcfc_sparse_index_driver.h"
 #include "vcfc_subset_driver.h"
+#include "vcfc_counts_driver.h"
 
 hipError_t vcfc_sparse_plan_launch(const uint8_t *recs, const uint64_t *rec_off, uint64_t n, uint64_t data_start,
                                    uint64_t *file_off, uint8_t *prefix, uint64_t *status, hipStream_t s);
@@ -1449,6 +1450,84 @@ int vcfc_decode_samples_device(const uint8_t *d_in, uint64_t in_bytes, const uin
         return VCFC_E_HIP;
     if (vcfc_subset_plan(a, s) != hipSuccess) return VCFC_E_HIP;
     return vcfc_subset_write(a, 0, n, s) == hipSuccess ? VCFC_OK : VCFC_E_HIP;
+}
+
+// ---- genotype counts; driver in vcfc_counts_driver.h -----------
+
+uint64_t vcfc_counts_workspace_size(uint64_t n_records, uint64_t samples) {
+    return vcfc_counts_workspace_layout(n_records, samples).total;
+}
+
+uint64_t vcfc_counts_lds_samples(void) { return VCFC_COUNTS_LDS_SAMPLES; }
+
+int vcfc_genotype_counts_device(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_rec_start,
+                                const uint8_t *d_select, uint64_t n, uint64_t samples, uint32_t *d_variant,
+                                uint64_t *d_sample, void *d_ws, uint64_t ws_bytes, uint64_t *d_err, void *stream) {
+    return vcfc_cnt::counts_device(d_in, in_bytes, d_rec_start, d_select, n, samples, d_variant, d_sample, d_ws, ws_bytes,
+                                   d_err, static_cast<hipStream_t>(stream));
+}
+
+int vcfc_genotype_counts_buffer(vcfc_ctx *c, const uint8_t *in, uint64_t n, int has_query, const char *ref,
+                                uint64_t ref_len, int has_range, uint64_t start, uint64_t end, uint64_t *rec_index,
+                                uint32_t *rows, uint64_t rows_cap, uint64_t *n_rows, uint64_t *sample_table,
+                                uint64_t sample_cap, uint64_t *n_samples, uint64_t *err_record) {
+    if (!c || (!in && n) || (has_query && !ref && ref_len) || ((!rec_index || !rows) && rows_cap) ||
+        (!sample_table && sample_cap) || !n_rows || !n_samples || !err_record)
+        return VCFC_E_ARG;
+    *n_rows = *n_samples = 0;
+    *err_record = ~0ull;
+    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
+    const vcfc_cnt::Query q{reinterpret_cast<const uint8_t *>(ref), ref_len, has_range, start, end};
+    vcfc_cnt::Result R;
+    uint64_t data_off = 0, S = 0;
+    CtxDecodeBuffers B(c);
+    const int st = vcfc_cnt::counts_file(in, n, has_query ? &q : nullptr, B, c->stream, R, &data_off, &S);
+    if (st != VCFC_OK && st != VCFC_E_FORMAT) return st;
+    *n_rows = R.index.size();
+    *n_samples = st == VCFC_OK ? S : 0;
+    *err_record = R.err_record;
+    if (*n_rows > rows_cap || *n_samples > sample_cap) return VCFC_E_NOSPACE;
+    if (*n_rows) {
+        memcpy(rec_index, R.index.data(), 8 * R.index.size());
+        memcpy(rows, R.rows.data(), 4 * R.rows.size());
+    }
+    if (st == VCFC_OK) memcpy(sample_table, R.samples.data(), 8 * R.samples.size());
+    return st;
+}
+
+int vcfc_genotype_counts_file(vcfc_ctx *c, const char *in_path, const char *variants_path, const char *samples_path,
+                              int has_query, const char *ref, uint64_t ref_len, int has_range, uint64_t start,
+                              uint64_t end) {
+    if (!c || !in_path || !variants_path || !samples_path || (has_query && !ref && ref_len)) return VCFC_E_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
+    const int vfd = open(variants_path, O_CREAT | O_TRUNC | O_WRONLY, 0644);
+    if (vfd < 0) return VCFC_E_IO;
+    const int sfd = open(samples_path, O_CREAT | O_TRUNC | O_WRONLY, 0644);
+    if (sfd < 0) {
+        close(vfd);
+        return VCFC_E_IO;
+    }
+    MappedFile f;
+    int st = f.open_ro(in_path);
+    if (!st) {
+        const vcfc_cnt::Query q{reinterpret_cast<const uint8_t *>(ref), ref_len, has_range, start, end};
+        vcfc_cnt::Result R;
+        uint64_t data_off = 0, S = 0;
+        CtxDecodeBuffers B(c);
+        st = vcfc_cnt::counts_file(f.p, f.n, has_query ? &q : nullptr, B, c->stream, R, &data_off, &S);
+        if (data_off && S && (st == VCFC_OK || st == VCFC_E_FORMAT)) {   // past the header
+            std::vector<uint8_t> text;
+            vcfc_cnt::render_variants(f.p + data_off, R, text);
+            if (write_all_at(vfd, text.data(), text.size(), 0)) st = VCFC_E_IO;
+            if (st == VCFC_OK) {
+                vcfc_cnt::render_samples(f.p, data_off, S, R, text);
+                if (write_all_at(sfd, text.data(), text.size(), 0)) st = VCFC_E_IO;
+            }
+        }
+    }
+    if (close(vfd) != 0 && !st) st = VCFC_E_IO;
+    if (close(sfd) != 0 && !st) st = VCFC_E_IO;
+    return st;
 }
 
 int vcfc_query_match_device(const uint8_t *d_in, const uint64_t *d_rec_start, uint64_t n, const uint8_t *d_ref,

@@ -279,6 +279,47 @@ hipError_t vcfc_subset_plan(const VcfcSubsetArgs &a, hipStream_t s);
 hipError_t vcfc_subset_write(const VcfcSubsetArgs &a, uint64_t first, uint64_t last, hipStream_t s);
 
 // ---------------------------------------------------------------------------
+// Genotype counts (vcfc_counts.hip): per record a row of eight
+// counters, per sample five, both taken from the run-length code without
+// decoding it.  A record that is not regular is reported in
+// err.
+struct VcfcCountsArgs {
+    const uint8_t *in;          // data section bytes (device)
+    uint64_t n_bytes;
+    const uint64_t *rec_start;  // n + 1 record offsets into `in`
+    const uint8_t *select;      // nullptr, or per record: 0 = skip it (zero row, not counted, not checked)
+    uint64_t n;                 // records (< 2^32)
+    uint64_t S;                 // samples declared by the header line (1 <= S < 2^30)
+    uint32_t *variant;          // nullptr, or 8 n words: n00 n01 n10 n11 n_other AN AC1 AC_other per record
+    uint64_t *sample;           // nullptr, or 5 S words, ADDED to: c00 c01 c10 c11 c_other per sample
+    // workspace (vcfc_counts_workspace_layout)
+    uint64_t *hist;             // 4 S words, class-major: this call's c01 c10 c11 c_other
+    uint64_t *counted;          // records counted by this call
+    uint32_t *seq_list;         // records left to the byte-serial path
+    uint32_t *seq_count;
+    uint64_t *err;              // min over records of (i << 8 | 3): not regular
+};
+// samples whose 4 x uint32 counters fit the LDS tile k_cnt_scan is built with
+// (16 S bytes <= 40 KiB); above it the histogram takes global atomics
+#define VCFC_COUNTS_LDS_SAMPLES 2560u
+
+struct VcfcCountsLayout {
+    uint64_t hist, counted, seq_list, seq_count, err, total;
+};
+VcfcCountsLayout vcfc_counts_workspace_layout(uint64_t n, uint64_t S);
+// Point a's workspace arrays into ws (err included).
+inline void vcfc_counts_args_workspace(VcfcCountsArgs &a, uint8_t *ws, const VcfcCountsLayout &L) {
+    a.hist = reinterpret_cast<uint64_t *>(ws + L.hist);
+    a.counted = reinterpret_cast<uint64_t *>(ws + L.counted);
+    a.seq_list = reinterpret_cast<uint32_t *>(ws + L.seq_list);
+    a.seq_count = reinterpret_cast<uint32_t *>(ws + L.seq_count);
+    a.err = reinterpret_cast<uint64_t *>(ws + L.err);
+}
+// one scan of every (selected) record: rows, the sample table, err (no host
+// synchronisation)
+hipError_t vcfc_counts_run(const VcfcCountsArgs &a, hipStream_t s);
+
+// ---------------------------------------------------------------------------
 // Range query (vcfc_decode.hip; reference query_compressed_file,
 // src/main.cpp:3777-3929).  `ref` is device memory.
 struct VcfcQuery {

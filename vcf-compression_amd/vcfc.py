@@ -53,6 +53,8 @@ EXPORTS = [
     "vcfc_sample_columns", "vcfc_subset_workspace_size", "vcfc_decode_samples_device",
     "vcfc_decompress_samples_buffer", "vcfc_decompress_samples_file",
     "vcfc_query_samples_buffer", "vcfc_query_samples_file",
+    "vcfc_counts_workspace_size", "vcfc_counts_lds_samples", "vcfc_genotype_counts_device",
+    "vcfc_genotype_counts_buffer", "vcfc_genotype_counts_file",
 ]
 LINE_INDEX_HOP, LINE_INDEX_SCAN = 0, 1                       # include/vcfc.h VCFC_LINE_INDEX_*
 TRACE_INGEST, TRACE_DEVICE, TRACE_SPARSE_QUERY = 1, 2, 4     # include/vcfc.h VCFC_TRACE_*
@@ -123,12 +125,22 @@ def lib():
             "vcfc_query_samples_buffer": [vp, vp, u64, ctypes.c_char_p, u64, ctypes.c_int, u64, u64, vp, u64, vp, u64,
                                           ctypes.POINTER(u64)],
             "vcfc_query_samples_file": [vp, ctypes.c_char_p, ctypes.c_char_p, u64, ctypes.c_int, u64, u64, vp, u64,
-                                        ctypes.c_int]}
+                                        ctypes.c_int],
+            # genotype counts
+            "vcfc_counts_workspace_size": [u64, u64],
+            "vcfc_counts_lds_samples": [],
+            "vcfc_genotype_counts_device": [vp, u64, vp, vp, u64, u64, vp, vp, vp, u64, vp, vp],
+            "vcfc_genotype_counts_buffer": [vp, vp, u64, ctypes.c_int, ctypes.c_char_p, u64, ctypes.c_int, u64, u64, vp,
+                                            vp, u64, ctypes.POINTER(u64), vp, u64, ctypes.POINTER(u64),
+                                            ctypes.POINTER(u64)],
+            "vcfc_genotype_counts_file": [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int,
+                                          ctypes.c_char_p, u64, ctypes.c_int, u64, u64]}
     for name, args in late.items():
         if hasattr(L, name):
             getattr(L, name).argtypes = args
     for name in ("vcfc_index_workspace_size", "vcfc_sparse_index_workspace_size", "vcfc_sparse_index_offset",
-                 "vcfc_decode_sizes_workspace_size", "vcfc_subset_workspace_size"):
+                 "vcfc_decode_sizes_workspace_size", "vcfc_subset_workspace_size", "vcfc_counts_workspace_size",
+                 "vcfc_counts_lds_samples"):
         if hasattr(L, name):
             getattr(L, name).restype = u64
     L.vcfc_record_hash_device.argtypes = [vp, vp, u64, vp, vp]
@@ -525,6 +537,46 @@ class Context:
                                                    len(query.reference_name), int(query.has_range), query.start,
                                                    query.end, c.ctypes.data, len(c), out_fd))
 
+    def genotype_counts_buffer(self, data, query=None):
+        """genotype-counts over .vcfc bytes, every record or
+        (query: a VcfCoordinateQuery or a coordinate string) the matching
+        ones.  Returns (status, record_indices, rows, samples): the counted
+        records' file indices (uint64[n]), their rows n00 n01 n10 n11 n_other
+        AN AC1 AC_other (uint32[n, 8]) and the per-sample table c00 c01 c10
+        c11 c_other (uint64[S, 5]).  On VCFC_E_FORMAT the rows are those
+        before the failing record (`last_counts_record`: its file index) and
+        samples is None; any other failure returns no rows."""
+        if query is not None and not isinstance(query, VcfCoordinateQuery):
+            query = parse_coordinate_string(query)
+        src = np.frombuffer(data, dtype=np.uint8)
+        ref = query.reference_name if query is not None else b""
+        cap, scap = len(data) // 12 + 16, 4096
+        while True:
+            idx, rows = np.zeros(cap, dtype=np.uint64), np.zeros((cap, 8), dtype=np.uint32)
+            tab = np.zeros((scap, 5), dtype=np.uint64)
+            n, ns, bad = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+            st = _need("vcfc_genotype_counts_buffer")(
+                self._h, src.ctypes.data, len(data), int(query is not None), ref, len(ref),
+                int(query.has_range) if query is not None else 0, query.start if query is not None else 0,
+                query.end if query is not None else 0, idx.ctypes.data, rows.ctypes.data, cap, ctypes.byref(n),
+                tab.ctypes.data, scap, ctypes.byref(ns), ctypes.byref(bad))
+            if st == E_NOSPACE and (n.value > cap or ns.value > scap):
+                cap, scap = max(cap, n.value), max(scap, ns.value)
+                continue
+            self.last_counts_record = bad.value
+            return st, idx[:n.value].copy(), rows[:n.value].copy(), tab[:ns.value].copy() if st == OK else None
+
+    def genotype_counts_file(self, in_path, variants_path, samples_path, query=None):
+        """As `main genotype-counts <in.vcfc> <variants.tsv> <samples.tsv>
+        [<query>]`: both TSV files (include/vcfc.h vcfc_genotype_counts_file)."""
+        if query is not None and not isinstance(query, VcfCoordinateQuery):
+            query = parse_coordinate_string(query)
+        ref = query.reference_name if query is not None else b""
+        raise_for(_need("vcfc_genotype_counts_file")(
+            self._h, in_path.encode(), variants_path.encode(), samples_path.encode(), int(query is not None), ref,
+            len(ref), int(query.has_range) if query is not None else 0, query.start if query is not None else 0,
+            query.end if query is not None else 0))
+
     def sparse_query_status(self, in_path, query):
         """query_sparse_file_fd (reference src/main.cpp:235-582) over a sparse
         file: (status, stdout bytes); E_FORMAT where the reference throws (the
@@ -862,3 +914,22 @@ def decode_samples_device(d_in, in_bytes, d_rec_start, d_select, n, samples, col
     c = np.asarray(cols, dtype=np.uint32)
     return _need("vcfc_decode_samples_device")(d_in, in_bytes, d_rec_start, d_select, n, samples, c.ctypes.data, len(c),
                                                d_out, out_cap, d_line_off, d_ws, ws_bytes, d_err, stream)
+
+
+def counts_workspace_size(n_records, samples):
+    return int(_need("vcfc_counts_workspace_size")(n_records, samples))
+
+
+def counts_lds_samples():
+    """The largest sample count whose histogram the counts kernel sums in LDS."""
+    return int(_need("vcfc_counts_lds_samples")())
+
+
+def genotype_counts_device(d_in, in_bytes, d_rec_start, d_select, n, samples, d_variant, d_sample, d_ws, ws_bytes, d_err,
+                           stream=0):
+    """Rows (d_variant: 8 n uint32) and the per-sample table (d_sample: 5 S
+    uint64, added to) of device-resident records (include/vcfc.h
+    vcfc_genotype_counts_device); d_select, d_variant, d_sample may be None.
+    Returns the status; enqueued on `stream`."""
+    return _need("vcfc_genotype_counts_device")(d_in, in_bytes, d_rec_start, d_select, n, samples, d_variant, d_sample,
+                                                d_ws, ws_bytes, d_err, stream)
