@@ -210,11 +210,14 @@ def column_sets(S, seed=0):
     return out
 
 
-def rec(req, samples_bytes, lf=b"\n"):
+def rec(req, samples_bytes, lf=b"\n", reqlen=None, flags=(0xC0, 0xC0)):
+    """A record; reqlen / flags: a REQ length field other than len(req), the
+    two header bytes' top bits other than 11 (LEN stays right either way)."""
     body = req + samples_bytes + lf
     L = len(body) + 4
-    return bytes([0xC0 | (L >> 24) & 0x3F, (L >> 16) & 0xFF, (L >> 8) & 0xFF, L & 0xFF, 0xC0 | (len(req) >> 24) & 0x3F,
-                  (len(req) >> 16) & 0xFF, (len(req) >> 8) & 0xFF, len(req) & 0xFF]) + body
+    n = len(req) if reqlen is None else reqlen
+    return bytes([flags[0] | (L >> 24) & 0x3F, (L >> 16) & 0xFF, (L >> 8) & 0xFF, L & 0xFF, flags[1] | (n >> 24) & 0x3F,
+                  (n >> 16) & 0xFF, (n >> 8) & 0xFF, n & 0xFF]) + body
 
 
 def req_of(i):
@@ -263,7 +266,30 @@ def hand_built():
                 [[0], [HS - 1, 3]]))
     out.append(("overshoot", hd + rec(req_of(0), fill(HS)) + rec(req_of(1), fill(HS - 3) + b"\x04"), [[0], [HS - 1]]))
     out.append(("bytes_after_items", hd + rec(req_of(0), fill(HS) + b"\x00"), [[0]]))
-    return out
+    return out + frame_edges()
+
+
+def frame_edges():
+    """(name, file bytes, column sets): the checks of a record's frame, one
+    edge record each between two valid records (a wrong classification also
+    shifts a neighbour).  Every edge record but the last is irregular."""
+    hd = D.header(HS)
+    items = fill(299) + b"\xe12|1\t" + fill(200, 0xA0) + fill(100, 0x80)
+    r = req_of(1)
+    f = r.split(b"\t")
+    long_req = b"\t".join(f[:7] + [b"X" * 2500] + f[8:])   # the sample section starts in a later staged piece
+    edges = [("req_zero", rec(r, items, reqlen=0)),
+             ("no_samples", rec(r, b"")),                        # 9 + req == len: the last byte is the LF
+             ("len_flags_10", rec(r, items, flags=(0x80, 0xC0))),
+             ("req_flags_10", rec(r, items, flags=(0xC0, 0x80))),
+             ("tabs8", rec(b"\t".join(f[:2] + f[3:]), items)),
+             ("tabs10", rec(b"\t".join(f[:3] + f[2:]), items)),
+             ("no_lf", rec(r, items, lf=b"\t")),
+             ("bytes9", rec(b"", b"", reqlen=1)),
+             ("bytes10", rec(b"A", b"")),
+             ("long_req", rec(long_req, items))]
+    sets = [[0], [HS - 1, 0, 299, 300], list(range(0, HS, 7))]
+    return [("frame_" + name, hd + rec(req_of(0), items) + e + rec(req_of(2), items), sets) for name, e in edges]
 
 
 def batch_files():
@@ -369,6 +395,11 @@ def check_hand_built(dec):
     for k in ("run_chain", "one_run_byte", "escape_at_edge", "last_token_lf", "empty_escape", "two_token_escape",
               "zero_counts"):
         assert subset(hb[k][0], [0])[0] == OK, k
+    lines = D.header(HS).count(b"\n")
+    for name, data, _ in frame_edges():   # the first record's line, then the stop; all three of long_req
+        st, out = subset(data, [299])
+        assert (st, out.count(b"\n") - lines) == ((OK, 3) if name == "frame_long_req" else (E_FORMAT, 1)), name
+        assert out.endswith(b"\t2|1\n"), name
     assert subset(hb["empty_escape"][0], [9, 10, 11])[1].endswith(b"\t0|0\t\t1|0\n" + req_of(1) + b"0|0\t0|0\t0|0\n")
     assert subset(hb["last_token_lf"][0], [HS - 1, 0])[1].endswith(b"\t2|2\t1|1\n" + req_of(1) + b"3|12345\t0|0\n")
 

@@ -32,7 +32,8 @@ def lib():
         return _lib
     os.makedirs(os.path.dirname(SO), exist_ok=True)
     srcs = [os.path.join(CSRC, f) for f in ("vcfc_index.hip", "vcfc_decode.hip", "vcfc_encode.hip")]
-    deps = srcs + [os.path.join(CSRC, f) for f in ("vcfc_index_driver.h", "vcfc_decode_driver.h", "vcfc_device.h")] + \
+    deps = srcs + [os.path.join(CSRC, f) for f in ("vcfc_index_driver.h", "vcfc_decode_driver.h", "vcfc_decode_dev.h",
+                                                   "vcfc_device.h")] + \
         [os.path.join(EMU_DIR, f) for f in ("emu.cpp", "emu.h", "emu_index_api.cpp", "vcfc_wave.h", "hip/hip_runtime.h")]
     with open(SO + ".lock", "w") as lk:
         fcntl.flock(lk, fcntl.LOCK_EX)

@@ -37,7 +37,8 @@ def lib():
     srcs = [os.path.join(CSRC, f) for f in ("vcfc_sparse_index.hip", "vcfc_index.hip", "vcfc_decode.hip",
                                             "vcfc_encode.hip")]
     deps = srcs + [os.path.join(CSRC, f) for f in ("vcfc_sparse_index_driver.h", "vcfc_index_driver.h",
-                                                   "vcfc_index_dev.h", "vcfc_decode_driver.h", "vcfc_device.h")] + \
+                                                   "vcfc_index_dev.h", "vcfc_decode_dev.h", "vcfc_decode_driver.h",
+                                                   "vcfc_device.h")] + \
         [os.path.join(EMU_DIR, f) for f in ("emu.cpp", "emu.h", "emu_sparse_index_api.cpp", "vcfc_wave.h",
                                             "hip/hip_runtime.h")]
     with open(SO + ".lock", "w") as lk:

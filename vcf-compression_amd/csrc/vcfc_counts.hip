@@ -164,21 +164,10 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) { return vw::readlane(v
 template <int HIST>
 __device__ __forceinline__ bool count_one(const VcfcCountsArgs &a, uint64_t i, uint8_t *sb, uint32_t *tile) {
     const uint32_t l = vw::lane_id();
-    const uint64_t rs_abs = a.rec_start[i], re_abs = a.rec_start[i + 1];
-    if (re_abs - rs_abs < 10 || re_abs - rs_abs >= (1ull << 31)) return false;
-    const uint64_t rbase = rs_abs & ~15ull;
-    const uint32_t rs = (uint32_t)(rs_abs - rbase), re = (uint32_t)(re_abs - rbase);
-    Staged sg;
-    sg.init(sb, a.in + rbase, re);
-    sg.load(rs);
-    const uint32_t h0 = sg.at(rs), h4 = sg.at(rs + 4);
-    const uint32_t req = ((h4 & 0x3Fu) << 24) | (sg.at(rs + 5) << 16) | (sg.at(rs + 6) << 8) | sg.at(rs + 7);
-    if ((h0 >> 6) != 3u || (h4 >> 6) != 3u || req == 0 || 9 + (uint64_t)req >= re - rs) return false;
-    uint32_t tabs, slen;
-    scan_req(sg, rs + 8, req, &tabs, &slen);
-    sg.need(re - 1);
-    if (tabs != 9 || slen != req || sg.at(re - 1) != '\n') return false;
-    const uint32_t s0 = rs + 8 + req, s1 = re - 1;
+    RecFrame f;
+    if (!frame_open(f, sb, a.in, a.rec_start[i], a.rec_start[i + 1]) || f.slen != f.req) return false;   // (no NUL in REQ)
+    Staged &sg = f.sg;
+    const uint32_t s0 = f.s0(), s1 = f.s1();
     Acc acc;
     uint32_t got;
     const uint32_t stop = scan_items<HIST>(a, sg, s0, s1, ~0u, 1u, tile, acc, &got);
@@ -264,70 +253,40 @@ __global__ __launch_bounds__(64 * CNT_WAVES) void k_cnt_scan(VcfcCountsArgs a) {
     }
 }
 
-// The byte-serial walk of a regular record [rs, re): its row
-// and (HIST) its columns; false where the record is not regular (the row is
-// not written; the table is not meaningful then).
+// The byte-serial walk of a regular record (walk_regular, vcfc_decode_dev.h)
+// [rs, re): its row and (HIST) its columns; false where the record is not
+// regular (the row is not written; the table is not meaningful then).  (The
+// walk's length bound is the 32-bit counters' bound, see above.)
 template <bool HIST>
 __device__ bool cnt_walk(const VcfcCountsArgs &a, uint64_t i, uint64_t rs, uint64_t re) {
     const uint8_t *in = a.in;
-    const uint64_t S = a.S;
-    if (re - rs < 10 || re - rs >= (1ull << 31)) return false;   // (the 32-bit counters' bound, see above)
-    const uint8_t *h = in + rs;
-    if ((h[0] >> 6) != 3u || (h[4] >> 6) != 3u) return false;
-    const uint32_t req = ((uint32_t)(h[4] & 0x3Fu) << 24) | ((uint32_t)h[5] << 16) | ((uint32_t)h[6] << 8) | h[7];
-    if (req == 0 || 9 + (uint64_t)req >= re - rs) return false;
-    const uint64_t end = re - 1;   // the record's last byte: its LF
-    if (in[end] != '\n') return false;
-    uint32_t tabs = 0;
-    for (uint32_t k = 0; k < req; k++) {
-        const uint8_t b = in[rs + 8 + k];
-        if (b == 0) return false;
-        tabs += b == '\t';
-    }
-    if (tabs != 9) return false;
-    uint64_t ip = rs + 8 + req, got = 0;
     uint32_t n01 = 0, n10 = 0, n11 = 0, nother = 0, nesc = 0, an = 0, ac1 = 0, aco = 0;
-    while (got < S) {
-        if (ip >= end) return false;
-        const uint8_t b = in[ip++];
-        if ((b & 0xE0u) == 0xE0u) {
-            const uint32_t uc = b & 0x1Fu;
-            if (got + uc > S) return false;
-            for (uint32_t u = 0; u < uc; u++) {
-                const uint64_t t0 = ip;
-                while (ip < end && in[ip] != '\t' && in[ip] != '\n') ip++;
-                // in[ip] is a TAB, or an LF: only the record's last token may end at the closing LF
-                if (in[ip] == '\n' && (ip != end || u + 1 != uc || got + 1 != S)) return false;
-                const uint32_t k = tok_count([&](uint32_t q) { return (uint32_t)in[t0 + q]; }, (uint32_t)(ip - t0), an, ac1, aco);
-                nesc++;
-                n01 += k == 1;
-                n10 += k == 2;
-                n11 += k == 3;
-                nother += k == 4;
-                if (HIST && k) hist_add<H_GLOBAL>(a, nullptr, k, (uint32_t)got, 1u);
-                got++;
-                if (in[ip] == '\t') ip++;
-            }
-        } else {
-            const uint32_t cnt = b < 0x80u ? b : (b & 0x1Fu);
-            if (got + cnt > S) return false;
-            if (b >= 0x80u) {
-                const uint32_t m = b & 0xE0u;
-                const uint32_t k = m == 0xA0u ? 1u : m == 0xC0u ? 2u : 3u;
-                n01 += k == 1 ? cnt : 0u;
-                n10 += k == 2 ? cnt : 0u;
-                n11 += k == 3 ? cnt : 0u;
-                ac1 += k == 3 ? 2 * cnt : cnt;
-                if (HIST)
-                    for (uint32_t t = 0; t < cnt; t++) hist_add<H_GLOBAL>(a, nullptr, k, (uint32_t)got + t, 1u);
-            }
-            got += cnt;
-        }
-    }
-    if (ip != end) return false;   // the items end at the closing LF
+    const bool ok = walk_regular<true>(
+        in, rs, re, a.S,
+        [&](uint64_t got, const uint8_t *src, uint32_t len) {
+            const uint32_t k = tok_count([&](uint32_t q) { return (uint32_t)src[q]; }, len, an, ac1, aco);
+            nesc++;
+            n01 += k == 1;
+            n10 += k == 2;
+            n11 += k == 3;
+            nother += k == 4;
+            if (HIST && k) hist_add<H_GLOBAL>(a, nullptr, k, (uint32_t)got, 1u);
+        },
+        [&](uint8_t b, uint64_t got, uint32_t cnt) {
+            if (b < 0x80u) return;   // a 0|0 run
+            const uint32_t m = b & 0xE0u;
+            const uint32_t k = m == 0xA0u ? 1u : m == 0xC0u ? 2u : 3u;
+            n01 += k == 1 ? cnt : 0u;
+            n10 += k == 2 ? cnt : 0u;
+            n11 += k == 3 ? cnt : 0u;
+            ac1 += k == 3 ? 2 * cnt : cnt;
+            if (HIST)
+                for (uint32_t t = 0; t < cnt; t++) hist_add<H_GLOBAL>(a, nullptr, k, (uint32_t)got + t, 1u);
+        });
+    if (!ok) return false;
     if (a.variant) {
         uint32_t *row = a.variant + 8 * i;
-        const uint32_t S32 = (uint32_t)S;
+        const uint32_t S32 = (uint32_t)a.S;
         row[0] = S32 - n01 - n10 - n11 - nother; row[1] = n01; row[2] = n10; row[3] = n11;
         row[4] = nother; row[5] = 2u * (S32 - nesc) + an; row[6] = ac1; row[7] = aco;
     }

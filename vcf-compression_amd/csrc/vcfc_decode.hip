@@ -32,7 +32,7 @@
 #include <type_traits>
 #include <vcfc_wave.h>   // angle brackets: tests/simt_emu shadows it
 #include "vcfc_device.h"
-#include "vcfc_decode_dev.h"   // scan_window, Staged, scan_req (shared with vcfc_subset.hip)
+#include "vcfc_decode_dev.h"   // be30, Staged, scan_window, RecFrame, SEL_R
 
 namespace {
 
@@ -48,10 +48,6 @@ constexpr uint32_t DS_SKIP = 5;     // not selected: no line
 
 // result of dec_line_seq
 constexpr int DL_OK = 0, DL_END = 1, DL_ERR = 2;
-
-__device__ __forceinline__ uint32_t be30(const uint8_t *h) {
-    return ((uint32_t)(h[0] & 0x3Fu) << 24) | ((uint32_t)h[1] << 16) | ((uint32_t)h[2] << 8) | h[3];
-}
 
 // One data line, byte-serial, exactly as decompress2_data_line
 // (compress.cpp:741-986): from the 8 header bytes at in[p] through the
@@ -130,8 +126,6 @@ __device__ int dec_line_seq(const uint8_t *in, uint64_t n, uint64_t p, uint64_t 
     return DL_OK;
 }
 
-// (scan_window, Staged and scan_req: vcfc_decode_dev.h)
-
 // FULL = 0 ("light"): the sample section is not scanned; a record whose
 // header, REQ and final LF look right is assumed simple, and k_dec_write
 // verifies the assumption while it writes (code 4 in err: rerun exactly).
@@ -141,33 +135,14 @@ __device__ __forceinline__ void plan_one(const VcfcDecodeArgs &a, uint64_t i, ui
     const uint64_t rs_abs = a.rec_start[i], re_abs = a.rec_start[i + 1];
     bool simple = false;
     uint64_t size = 0;
-    if (re_abs - rs_abs >= 10 && re_abs - rs_abs < (1ull << 31) && a.S > 0 && a.S < (1ull << 31)) {
-        const uint64_t rbase = rs_abs & ~15ull;
-        const uint32_t rs = (uint32_t)(rs_abs - rbase), re = (uint32_t)(re_abs - rbase);
-        Staged sg;
-        sg.init(sb, a.in + rbase, re);
-        sg.load(rs);
-        const uint32_t h0 = sg.at(rs), h4 = sg.at(rs + 4);
-        const uint32_t req = ((h4 & 0x3Fu) << 24) | (sg.at(rs + 5) << 16) | (sg.at(rs + 6) << 8) | sg.at(rs + 7);
-        if ((h0 >> 6) == 3u && (h4 >> 6) == 3u && req > 0 && 9 + (uint64_t)req < re - rs) {
-            uint32_t tabs, slen;
-            scan_req(sg, rs + 8, req, &tabs, &slen);
-            sg.need(re - 1);
-            if (tabs == 9 && sg.at(re - 1) == '\n') {
-                simple = true;
-                if (FULL) {
-                    ItemState st;
-                    const uint32_t s0 = rs + 8 + req, s1 = re - 1;
-                    for (uint32_t cur = s0 & ~3u; cur < s1 && !st.bad; cur += 256) {
-                        sg.need(cur, 256 + 8);
-                        const uint32_t b = umin32(cur + 256, s1);
-                        (void)scan_window(sg.at4(cur + 4 * l), cur, s0, b, s1, st);
-                    }
-                    simple = !st.bad && st.got == a.S;
-                }
-                size = slen + 4 * a.S;
-            }
+    RecFrame f;
+    if (a.S > 0 && a.S < (1ull << 31) && frame_open(f, sb, a.in, rs_abs, re_abs)) {
+        simple = true;
+        if (FULL) {
+            const ItemState st = scan_items_plain(f);
+            simple = !st.bad && st.got == a.S;
         }
+        size = f.slen + 4 * a.S;
     }
     if (l == 0) {
         a.st[i] = simple ? DS_SIMPLE : DS_SEQ;
@@ -179,13 +154,8 @@ __device__ __forceinline__ void plan_one(const VcfcDecodeArgs &a, uint64_t i, ui
     }
 }
 
-// Selected decodes (a.select set, the range query): a grid of n / SEL_R
-// waves; wave g takes records g, g + G, g + 2G, ... (G = waves in the grid)
-// and plans / writes the selected ones, so an unselected record costs a flag
-// read instead of a wave launch, and a contiguous selected range (a POS
-// window) spreads over all waves.
-constexpr uint32_t SEL_R = 8;
-
+// (selected decodes, a.select set: the dealing of SEL_R records to a wave,
+// vcfc_decode_dev.h)
 template <bool FULL, bool SEL>
 __global__ __launch_bounds__(256) void k_dec_plan(VcfcDecodeArgs a) {
     __shared__ __attribute__((aligned(16))) uint8_t sbuf[DEC_WAVES * SBUF];
@@ -292,13 +262,11 @@ __device__ __forceinline__ void write_one(const VcfcDecodeArgs &a, uint64_t i, c
         }
         return;
     }
-    const uint64_t rbase = rs_abs & ~15ull;
-    const uint32_t rs = (uint32_t)(rs_abs - rbase), re = (uint32_t)((PRE ? mt.re : a.rec_start[i + 1]) - rbase);
+    RecFrame f;
+    frame_stage(f, sb, a.in, rs_abs, PRE ? mt.re : a.rec_start[i + 1]);
+    Staged &sg = f.sg;
+    const uint32_t rs = f.rs, req = f.req;
     const uint32_t S = (uint32_t)a.S;
-    Staged sg;
-    sg.init(sb, a.in + rbase, re);
-    sg.load(rs);
-    const uint32_t req = ((sg.at(rs + 4) & 0x3Fu) << 24) | (sg.at(rs + 5) << 16) | (sg.at(rs + 6) << 8) | sg.at(rs + 7);
     const uint32_t slen = (uint32_t)(L1 - L0 - 4ull * S);   // REQ' = line - 4S
     // copy REQ', and check what a light plan assumed: 9 TABs in REQ, REQ'
     // ends at REQ's first NUL (an exact plan made both true)
@@ -386,7 +354,7 @@ __device__ __forceinline__ void write_one(const VcfcDecodeArgs &a, uint64_t i, c
         carry = vw::readlane(w[PL - 1], 63);
         vw::wave_sync();
     };
-    const uint32_t s0 = rs + 8 + req, s1 = re - 1;
+    const uint32_t s0 = f.s0(), s1 = f.s1();
     ItemState st;
 #ifdef VCFC_DIAG_DEC_NOSCAN   // (diagnostic, wrong output: the line's tile stores without the item scan)
     for (; j0 + TB < S; j0 += TB) tile_out(std::false_type(), TB);

@@ -1,8 +1,12 @@
 // vcfc_decode_dev.h -- device-side parsers of a .vcfc record shared by the
-// decoder (vcfc_decode.hip) and the sample-subset decoder (vcfc_subset.hip):
-// the wave-parallel scan of a record's sample items, the record staged
-// through LDS, and the REQ scan.  Everything here has internal linkage
-// (anonymous namespace): each kernel file compiles its own copy.
+// decoder (vcfc_decode.hip), the sample-subset decoder (vcfc_subset.hip),
+// genotype-counts (vcfc_counts.hip) and gap-analysis (vcfc_sparse_index.hip):
+// the big-endian 30-bit header fields, the wave-parallel scan of a record's
+// sample items, the record staged through LDS, the frame of a simple record
+// (header bits, REQ, closing LF), the byte-serial walk of a regular record,
+// and the records a wave takes in selected mode.  Everything here has
+// internal linkage (anonymous namespace): each kernel file compiles its own
+// copy.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -15,6 +19,11 @@ constexpr uint32_t SBUF = SB + 48;         // + look-ahead, 16-B alignment slack
 
 __device__ __forceinline__ uint64_t umin64(uint64_t a, uint64_t b) { return a < b ? a : b; }
 __device__ __forceinline__ uint32_t umin32(uint32_t a, uint32_t b) { return a < b ? a : b; }
+
+// a header field (LEN, REQ length): 30 bits big-endian below the two flag bits
+__device__ __forceinline__ uint32_t be30(const uint8_t *h) {
+    return ((uint32_t)(h[0] & 0x3Fu) << 24) | ((uint32_t)h[1] << 16) | ((uint32_t)h[2] << 8) | h[3];
+}
 
 // bit i set <=> byte i of w is zero (exact)
 // (the four flags gathered by one v_dot4_u32_u8, round 5: 6 VALU fewer than
@@ -153,5 +162,114 @@ __device__ __forceinline__ void scan_req(Staged &sg, uint32_t r0, uint32_t req, 
     *tabs = t;
     *slen = z;
 }
+
+// A record staged for a wave, positions relative to rbase: the record is
+// [rs, re), its REQ bytes [rs + 8, rs + 8 + req), its sample items [s0(),
+// s1()) and byte s1() its closing LF.  slen: REQ's C-string length (req where
+// REQ holds no NUL).
+struct RecFrame {
+    uint32_t rs, re, req, slen;
+    Staged sg;
+    __device__ __forceinline__ uint32_t s0() const { return rs + 8 + req; }
+    __device__ __forceinline__ uint32_t s1() const { return re - 1; }
+};
+
+// Stage the record in[rs_abs, re_abs) into sb and read its REQ length; no
+// checks (the writers: the planner has validated the record; slen is not set).
+__device__ __forceinline__ void frame_stage(RecFrame &f, uint8_t *sb, const uint8_t *in, uint64_t rs_abs, uint64_t re_abs) {
+    const uint64_t rbase = rs_abs & ~15ull;
+    f.rs = (uint32_t)(rs_abs - rbase);
+    f.re = (uint32_t)(re_abs - rbase);
+    f.sg.init(sb, in + rbase, f.re);
+    f.sg.load(f.rs);
+    f.req = be30(f.sg.lds + (f.rs + 4 - f.sg.cbase));
+}
+
+// The frame of a simple record: 10 <= length < 2^31, both header bytes' flag
+// bits set, REQ not empty and ending before the record's last byte, exactly 9
+// TABs in REQ, the last byte an LF.  (The last byte is touched after the REQ
+// scan: a record longer than one staged piece is then loaded in order.)
+__device__ __forceinline__ bool frame_open(RecFrame &f, uint8_t *sb, const uint8_t *in, uint64_t rs_abs, uint64_t re_abs) {
+    if (re_abs - rs_abs < 10 || re_abs - rs_abs >= (1ull << 31)) return false;
+    frame_stage(f, sb, in, rs_abs, re_abs);
+    if ((f.sg.at(f.rs) >> 6) != 3u || (f.sg.at(f.rs + 4) >> 6) != 3u || f.req == 0 || 9 + (uint64_t)f.req >= f.re - f.rs)
+        return false;
+    uint32_t tabs;
+    scan_req(f.sg, f.rs + 8, f.req, &tabs, &f.slen);
+    f.sg.need(f.re - 1);
+    return tabs == 9 && f.sg.at(f.re - 1) == '\n';
+}
+
+// Every window of the frame's sample items, up to the first that is not
+// simple (bad): the record is simple when !bad && got == S.
+__device__ __forceinline__ ItemState scan_items_plain(RecFrame &f) {
+    const uint32_t l = vw::lane_id();
+    const uint32_t s0 = f.s0(), s1 = f.s1();
+    ItemState st;
+    for (uint32_t cur = s0 & ~3u; cur < s1 && !st.bad; cur += 256) {
+        f.sg.need(cur, 256 + 8);
+        const uint32_t b = umin32(cur + 256, s1);
+        (void)scan_window(f.sg.at4(cur + 4 * l), cur, s0, b, s1, st);
+    }
+    return st;
+}
+
+// The byte-serial walk of a regular record in[rs, re), one
+// lane: false where the record is not regular.  REQCHK: REQ is checked too
+// (no NUL, exactly 9 TABs).  token(got, src, len): column got holds the
+// escaped token src[0, len); run(b, got, cnt): run byte b covers columns
+// [got, got + cnt).
+template <bool REQCHK, class FT, class FR>
+__device__ __forceinline__ bool walk_regular(const uint8_t *in, uint64_t rs, uint64_t re, uint64_t S, FT token, FR run) {
+    if (re - rs < 10 || re - rs >= (1ull << 31)) return false;
+    const uint8_t *h = in + rs;
+    if ((h[0] >> 6) != 3u || (h[4] >> 6) != 3u) return false;
+    const uint32_t req = be30(h + 4);
+    if (req == 0 || 9 + (uint64_t)req >= re - rs) return false;
+    const uint64_t end = re - 1;   // the record's last byte: its LF
+    if (in[end] != '\n') return false;
+    if (REQCHK) {
+        uint32_t tabs = 0;
+        for (uint32_t k = 0; k < req; k++) {
+            const uint8_t b = in[rs + 8 + k];
+            if (b == 0) return false;
+            tabs += b == '\t';
+        }
+        if (tabs != 9) return false;
+    }
+    uint64_t ip = rs + 8 + req, got = 0;
+    while (got < S) {
+        if (ip >= end) return false;
+        const uint8_t b = in[ip++];
+        if ((b & 0xE0u) == 0xE0u) {
+            const uint32_t uc = b & 0x1Fu;
+            if (got + uc > S) return false;
+            for (uint32_t u = 0; u < uc; u++) {
+                const uint64_t t0 = ip;
+                while (ip < end && in[ip] != '\t' && in[ip] != '\n') ip++;
+                // in[ip] is a TAB, or an LF: only the record's last token may end at the closing LF
+                if (in[ip] == '\n' && (ip != end || u + 1 != uc || got + 1 != S)) return false;
+                token(got, in + t0, (uint32_t)(ip - t0));
+                got++;
+                if (in[ip] == '\t') ip++;
+            }
+        } else {
+            const uint32_t cnt = b < 0x80u ? b : (b & 0x1Fu);
+            if (got + cnt > S) return false;
+            run(b, got, cnt);
+            got += cnt;
+        }
+    }
+    return ip == end;   // the items end at the closing LF
+}
+
+// Selected mode (a select flag per record, the range query): a grid of about
+// n / SEL_R waves; wave g of G takes records g, g + G, g + 2G, ... (SEL_R of
+// them: lane l < SEL_R reads the flag of the l-th) and handles the selected
+// ones, so an unselected record costs a flag read instead of a wave launch,
+// and a contiguous selected range (a POS window) spreads over all waves.
+// (The four selected kernels spell the dealing out, five lines each, around
+// what each does with an unselected record and with its metadata.)
+constexpr uint32_t SEL_R = 8;
 
 }  // namespace

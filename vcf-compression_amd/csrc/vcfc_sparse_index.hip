@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <vcfc_wave.h>   // angle brackets: tests/simt_emu shadows it
 #include "vcfc_device.h"
+#include "vcfc_decode_dev.h"   // be30
 
 namespace {
 
@@ -180,8 +181,7 @@ __global__ __launch_bounds__(256) void k_gap_fields(const uint8_t *in, const uin
     bool ok = re - rs > 8;
     uint64_t s0 = re;
     if (ok) {
-        const uint8_t *h = in + rs + 4;
-        const uint64_t req = ((uint64_t)(h[0] & 0x3Fu) << 24) | ((uint64_t)h[1] << 16) | ((uint64_t)h[2] << 8) | h[3];
+        const uint64_t req = be30(in + rs + 4);
         s0 = rs + 8 + req;
         ok = req > 0 && s0 < re;
         cnt = 8 + req;

@@ -32,7 +32,6 @@ namespace {
 
 constexpr int SUB_WAVES = 4;          // records per 256-thread block
 constexpr uint32_t SUB_TK = 512;      // words of the LDS line tile per wave
-constexpr uint32_t SUB_R = 8;         // selected mode: records per wave (as the decoder's SEL_R)
 
 constexpr uint32_t SS_SIMPLE = 0;     // line = REQ + 4K bytes, wave-parallel
 constexpr uint32_t SS_SEQ = 1;        // regular, byte-serial
@@ -41,32 +40,15 @@ constexpr uint32_t SS_SKIP = 5;       // not selected: no line
 
 constexpr int SW_SIZE = 0, SW_LEN = 1, SW_WRITE = 2;
 
-// The byte-serial walk of a regular record [rs, re): false
-// where the record is not regular.  SW_SIZE: checks everything, *size = the
-// line's bytes.  SW_LEN: scr[rank] = length of each chosen token.  SW_WRITE:
-// the chosen tokens and their TAB / LF to tok + scr[rank] (scr: offsets).
+// The byte-serial walk of a regular record (walk_regular, vcfc_decode_dev.h)
+// [rs, re): false where the record is not regular.  SW_SIZE: checks
+// everything, *size = the line's bytes.  SW_LEN: scr[rank] = length of each
+// chosen token.  SW_WRITE: the chosen tokens and their TAB / LF to tok +
+// scr[rank] (scr: offsets).
 template <int MODE>
 __device__ bool sub_walk(const VcfcSubsetArgs &a, uint64_t rs, uint64_t re, uint32_t *scr, uint8_t *tok,
                          uint64_t *size) {
-    const uint8_t *in = a.in;
-    const uint64_t S = a.S;
-    if (re - rs < 10 || re - rs >= (1ull << 31)) return false;
-    const uint8_t *h = in + rs;
-    if ((h[0] >> 6) != 3u || (h[4] >> 6) != 3u) return false;
-    const uint32_t req = ((uint32_t)(h[4] & 0x3Fu) << 24) | ((uint32_t)h[5] << 16) | ((uint32_t)h[6] << 8) | h[7];
-    if (req == 0 || 9 + (uint64_t)req >= re - rs) return false;
-    const uint64_t end = re - 1;   // the record's last byte: its LF
-    if (in[end] != '\n') return false;
-    if (MODE == SW_SIZE) {
-        uint32_t tabs = 0;
-        for (uint32_t k = 0; k < req; k++) {
-            const uint8_t b = in[rs + 8 + k];
-            if (b == 0) return false;
-            tabs += b == '\t';
-        }
-        if (tabs != 9) return false;
-    }
-    uint64_t ip = rs + 8 + req, got = 0, sum = 0;
+    uint64_t sum = 0;
     uint32_t c = 0;
     const uint32_t K = a.K;
     auto emit = [&](const uint8_t *src, uint32_t len) {   // the token of column csort[c]
@@ -80,34 +62,19 @@ __device__ bool sub_walk(const VcfcSubsetArgs &a, uint64_t rs, uint64_t re, uint
         }
         c++;
     };
-    while (got < S) {
-        if (ip >= end) return false;
-        const uint8_t b = in[ip++];
-        if ((b & 0xE0u) == 0xE0u) {
-            const uint32_t uc = b & 0x1Fu;
-            if (got + uc > S) return false;
-            for (uint32_t u = 0; u < uc; u++) {
-                const uint64_t t0 = ip;
-                while (ip < end && in[ip] != '\t' && in[ip] != '\n') ip++;
-                // in[ip] is a TAB, or an LF: only the record's last token may end at the closing LF
-                if (in[ip] == '\n' && (ip != end || u + 1 != uc || got + 1 != S)) return false;
-                if (c < K && a.csort[c] == got) emit(in + t0, (uint32_t)(ip - t0));
-                got++;
-                if (in[ip] == '\t') ip++;
-            }
-        } else {
-            const uint32_t cnt = b < 0x80u ? b : (b & 0x1Fu);
-            if (got + cnt > S) return false;
+    const bool ok = walk_regular<MODE == SW_SIZE>(
+        a.in, rs, re, a.S,
+        [&](uint64_t got, const uint8_t *src, uint32_t len) {
+            if (c < K && a.csort[c] == got) emit(src, len);
+        },
+        [&](uint8_t b, uint64_t got, uint32_t cnt) {
             const uint32_t m = b & 0xE0u;   // 0|1 -> 0xA0, 1|0 -> 0xC0, 1|1 -> 0x80, 0|0 < 0x80
             const uint8_t w[3] = {(uint8_t)(b < 0x80u || m == 0xA0u ? '0' : '1'), '|',
                                   (uint8_t)(b < 0x80u || m == 0xC0u ? '0' : '1')};
             while (c < K && a.csort[c] < got + cnt) emit(w, 3);
-            got += cnt;
-        }
-    }
-    if (ip != end) return false;   // the items end at the closing LF
-    if (MODE == SW_SIZE) *size = (uint64_t)req + sum + K;
-    return true;
+        });
+    if (ok && MODE == SW_SIZE) *size = (uint64_t)be30(a.in + rs + 4) + sum + K;
+    return ok;
 }
 
 // One record, one wave: simple (line size req + 4K) or queued.
@@ -116,30 +83,11 @@ __device__ __forceinline__ void plan_one(const VcfcSubsetArgs &a, uint64_t i, ui
     const uint64_t rs_abs = a.rec_start[i], re_abs = a.rec_start[i + 1];
     bool simple = false;
     uint64_t size = 0;
-    if (re_abs - rs_abs >= 10 && re_abs - rs_abs < (1ull << 31)) {
-        const uint64_t rbase = rs_abs & ~15ull;
-        const uint32_t rs = (uint32_t)(rs_abs - rbase), re = (uint32_t)(re_abs - rbase);
-        Staged sg;
-        sg.init(sb, a.in + rbase, re);
-        sg.load(rs);
-        const uint32_t h0 = sg.at(rs), h4 = sg.at(rs + 4);
-        const uint32_t req = ((h4 & 0x3Fu) << 24) | (sg.at(rs + 5) << 16) | (sg.at(rs + 6) << 8) | sg.at(rs + 7);
-        if ((h0 >> 6) == 3u && (h4 >> 6) == 3u && req > 0 && 9 + (uint64_t)req < re - rs) {
-            uint32_t tabs, slen;
-            scan_req(sg, rs + 8, req, &tabs, &slen);
-            sg.need(re - 1);
-            if (tabs == 9 && slen == req && sg.at(re - 1) == '\n') {
-                ItemState st;
-                const uint32_t s0 = rs + 8 + req, s1 = re - 1;
-                for (uint32_t cur = s0 & ~3u; cur < s1 && !st.bad; cur += 256) {
-                    sg.need(cur, 256 + 8);
-                    const uint32_t b = umin32(cur + 256, s1);
-                    (void)scan_window(sg.at4(cur + 4 * l), cur, s0, b, s1, st);
-                }
-                size = (uint64_t)req + 4ull * a.K;
-                simple = !st.bad && st.got == a.S && size <= 0xFFFFFFFFull;
-            }
-        }
+    RecFrame f;
+    if (frame_open(f, sb, a.in, rs_abs, re_abs) && f.slen == f.req) {   // (no NUL in REQ)
+        const ItemState st = scan_items_plain(f);
+        size = (uint64_t)f.req + 4ull * a.K;
+        simple = !st.bad && st.got == a.S && size <= 0xFFFFFFFFull;
     }
     if (l == 0) {
         a.st[i] = simple ? SS_SIMPLE : SS_SEQ;
@@ -151,9 +99,8 @@ __device__ __forceinline__ void plan_one(const VcfcSubsetArgs &a, uint64_t i, ui
     }
 }
 
-// Selected mode (a.select set): a grid of n / SUB_R waves; wave g takes
-// records g, g + G, g + 2G, ... (G = waves in the grid) and handles the
-// selected ones, as the decoder's selected kernels do.
+// (selected mode, a.select set: the dealing of SEL_R records to a wave,
+// vcfc_decode_dev.h)
 template <bool SEL>
 __global__ __launch_bounds__(256) void k_sub_plan(VcfcSubsetArgs a) {
     __shared__ __attribute__((aligned(16))) uint8_t sbuf[SUB_WAVES * SBUF];
@@ -167,7 +114,7 @@ __global__ __launch_bounds__(256) void k_sub_plan(VcfcSubsetArgs a) {
     const uint64_t G = (uint64_t)gridDim.x * SUB_WAVES;
     const uint32_t l = vw::lane_id();
     const uint64_t il = g + (uint64_t)l * G;
-    const bool mine = l < SUB_R && il < a.n;
+    const bool mine = l < SEL_R && il < a.n;
     const bool on = mine && a.select[il];
     if (mine && !on) { a.st[il] = SS_SKIP; a.line_size[il] = 0; }
     for (uint64_t m = vw::ballot(on); m; m &= m - 1)
@@ -206,12 +153,10 @@ __device__ __forceinline__ void write_one(const VcfcSubsetArgs &a, uint64_t i, u
         return;
     }
     if (rst != SS_SIMPLE) return;   // queued records: k_sub_wseq; no line otherwise
-    const uint64_t rbase = rs_abs & ~15ull;
-    const uint32_t rs = (uint32_t)(rs_abs - rbase), re = (uint32_t)(re_abs - rbase);
-    Staged sg;
-    sg.init(sb, a.in + rbase, re);
-    sg.load(rs);
-    const uint32_t req = ((sg.at(rs + 4) & 0x3Fu) << 24) | (sg.at(rs + 5) << 16) | (sg.at(rs + 6) << 8) | sg.at(rs + 7);
+    RecFrame f;
+    frame_stage(f, sb, a.in, rs_abs, re_abs);
+    Staged &sg = f.sg;
+    const uint32_t rs = f.rs, req = f.req;
     uint8_t *line = a.out + L0;
     // REQ verbatim (4 bytes per lane, 256 per step)
     for (uint32_t b0 = 0; b0 < req; b0 += 256) {
@@ -230,7 +175,7 @@ __device__ __forceinline__ void write_one(const VcfcSubsetArgs &a, uint64_t i, u
     }
     uint8_t *tok = line + req;
     const bool tile = K <= SUB_TK;
-    const uint32_t s0 = rs + 8 + req, s1 = re - 1;
+    const uint32_t s0 = f.s0(), s1 = f.s1();
     ItemState st;
     uint32_t c = 0;                          // cursor into csort (wave-uniform)
     uint32_t nextt = vw::readlane(tq, 0);    // csort[c]
@@ -308,7 +253,7 @@ __global__ __launch_bounds__(256) void k_sub_write(VcfcSubsetArgs a, uint64_t fi
     const uint64_t Gw = (uint64_t)gridDim.x * SUB_WAVES;
     const uint32_t l = vw::lane_id();
     const uint64_t il = first + g + (uint64_t)l * Gw;
-    const bool cand = l < SUB_R && il < last;
+    const bool cand = l < SEL_R && il < last;
     for (uint64_t m = vw::ballot(cand && a.select[il]); m; m &= m - 1)
         write_one(a, first + g + (uint64_t)__builtin_ctzll(m) * Gw, sb, G, W);
 }
@@ -338,7 +283,7 @@ __global__ __launch_bounds__(64) void k_sub_wseq(VcfcSubsetArgs a, uint64_t firs
             o += len + 1;
         }
         const uint8_t *h = a.in + rs;
-        const uint32_t req = ((uint32_t)(h[4] & 0x3Fu) << 24) | ((uint32_t)h[5] << 16) | ((uint32_t)h[6] << 8) | h[7];
+        const uint32_t req = be30(h + 4);
         uint8_t *line = a.out + L0;
         for (uint32_t k = 0; k < req; k++) line[k] = h[8 + k];
         (void)sub_walk<SW_WRITE>(a, rs, re, scr, line + req, &size);
@@ -376,7 +321,7 @@ hipError_t vcfc_subset_plan(const VcfcSubsetArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(k_sub_reset, dim3(1), dim3(64), 0, s, a.err, a.seq_count, a.n == 0 ? a.line_off : nullptr);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || a.n == 0) return e;
-    const uint64_t per_block = SUB_WAVES * (a.select ? SUB_R : 1);
+    const uint64_t per_block = SUB_WAVES * (a.select ? SEL_R : 1);
     const dim3 grid((unsigned)((a.n + per_block - 1) / per_block)), block(64 * SUB_WAVES);
     if (a.select) hipLaunchKernelGGL(k_sub_plan<true>, grid, block, 0, s, a);
     else hipLaunchKernelGGL(k_sub_plan<false>, grid, block, 0, s, a);
@@ -389,7 +334,7 @@ hipError_t vcfc_subset_plan(const VcfcSubsetArgs &a, hipStream_t s) {
 
 hipError_t vcfc_subset_write(const VcfcSubsetArgs &a, uint64_t first, uint64_t last, hipStream_t s) {
     if (last <= first) return hipSuccess;
-    const uint64_t per_block = SUB_WAVES * (a.select ? SUB_R : 1);
+    const uint64_t per_block = SUB_WAVES * (a.select ? SEL_R : 1);
     const dim3 grid((unsigned)((last - first + per_block - 1) / per_block)), block(64 * SUB_WAVES);
     if (a.select) hipLaunchKernelGGL(k_sub_write<true>, grid, block, 0, s, a, first, last);
     else hipLaunchKernelGGL(k_sub_write<false>, grid, block, 0, s, a, first, last);
