@@ -554,6 +554,76 @@ int vcfc_genotype_counts_file(vcfc_ctx *ctx, const char *in_vcfc, const char *va
                               int has_query, const char *ref, uint64_t ref_len, int has_range, uint64_t start,
                               uint64_t end);
 
+/* ---- region-list queries: one match pass over a whole BED /
+ * region file.  No reference counterpart.
+ * A region is what vcfc_parse_query yields; a record matches a region as the
+ * range query decides (an empty name matches any CHROM, no range matches any
+ * POS, else start <= POS <= end with POS parsed as there), and it matches a
+ * region set iff it matches one of its regions: the flags are the OR of
+ * vcfc_query_match_device's flags over the regions, the error word is
+ * vcfc_query_match_device's.  A region with start > end matches nothing; so
+ * does an empty set, which is not an error.  Output is in file order, each
+ * record at most once.
+ * Region text: one region per line.  LF ends a line, a CR before the LF is
+ * dropped, the last line may lack its LF.  Lines that are empty or start
+ * with '#', "track" or "browser" are skipped.  A line holding a TAB is BED,
+ * name TAB start TAB end [TAB ...], start and end 1..20 ASCII digits that fit
+ * 64 bits: the region name:[start + 1, end] (0-based, half-open; end <= start
+ * is an empty region).  Any other line goes whole to vcfc_parse_query.
+ * vcfc_regions_build writes the table, a position-independent blob (sorted
+ * distinct names; per name its intervals sorted by start, overlapping and
+ * adjacent ones merged; empty regions dropped).  VCFC_E_NOSPACE if table_cap
+ * is short (*table_bytes = the size needed); VCFC_E_ARG with *bad_line = the
+ * 1-based number of the first line that does not parse, or with *bad_line =
+ * 0 for a table of 4 GiB or more.  *n_regions = parsed regions, empty ones
+ * included. */
+int vcfc_regions_build(const char *text, uint64_t len, uint8_t *table, uint64_t table_cap, uint64_t *table_bytes,
+                       uint64_t *n_regions, uint64_t *bad_line);
+/* Device-resident match step.  vcfc_regions_upload validates the host table
+ * (magic word, counts and offsets inside table_bytes, names and starts
+ * sorted; anything else, or ws_bytes below vcfc_regions_workspace_size, is
+ * VCFC_E_ARG) and copies it into d_ws; the copy has left `table` when it
+ * returns.  vcfc_regions_match_device is vcfc_query_match_device with the
+ * uploaded table in place of one region: same d_flag, same *d_err; it is
+ * enqueued on `stream` without host synchronisation, resets *d_err in a
+ * kernel (capturable) and trusts what vcfc_regions_upload put into d_ws.
+ * n == 0 and an empty table are valid. */
+uint64_t vcfc_regions_workspace_size(uint64_t table_bytes);
+int vcfc_regions_upload(const uint8_t *table, uint64_t table_bytes, void *d_ws, uint64_t ws_bytes, void *stream);
+int vcfc_regions_match_device(const uint8_t *d_in, const uint64_t *d_rec_start, uint64_t n, const void *d_ws,
+                              uint64_t ws_bytes, uint8_t *d_flag, uint64_t *d_err, void *stream);
+/* A whole .vcfc against a built table (VCFC_E_ARG for a table
+ * vcfc_regions_upload would refuse).  vcfc_query_regions_*: the full lines
+ * (no header) of the matching records through the exact decoder.  The call
+ * stops with VCFC_E_FORMAT at the first record with a match error, and at the
+ * first matching record for which the decoder reports any error word; the
+ * lines of the matching records before it are written.  After all lines it
+ * returns VCFC_E_FORMAT where the LEN hops stop with 8 or more bytes left.
+ * It does not take the byte-serial continuation of the reference's walk:
+ * this action has no reference counterpart, so on a malformed file there is
+ * nothing to reproduce.  NOSPACE and file opening as vcfc_query_buffer /
+ * _file. */
+int vcfc_query_regions_buffer(vcfc_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const uint8_t *table,
+                              uint64_t table_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_len);
+int vcfc_query_regions_file(vcfc_ctx *ctx, const char *in_vcfc, const uint8_t *table, uint64_t table_bytes, int out_fd);
+/* vcfc_query_samples_* with a table in place of the region: only matching
+ * records need to be regular; a match error at record k stops there with
+ * VCFC_E_FORMAT; VCFC_E_NOSPACE, VCFC_E_ARG and file opening as there. */
+int vcfc_query_samples_regions_buffer(vcfc_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const uint8_t *table,
+                                      uint64_t table_bytes, const uint32_t *cols, uint64_t n_cols, uint8_t *out,
+                                      uint64_t out_cap, uint64_t *out_len);
+int vcfc_query_samples_regions_file(vcfc_ctx *ctx, const char *in_vcfc, const uint8_t *table, uint64_t table_bytes,
+                                    const uint32_t *cols, uint64_t n_cols, int out_fd);
+/* vcfc_genotype_counts_* with has_query = 1 and a table in place of the
+ * region: only matching records are counted and need to be regular; a match
+ * error at record k stops there with VCFC_E_FORMAT; outputs as there. */
+int vcfc_genotype_counts_regions_buffer(vcfc_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const uint8_t *table,
+                                        uint64_t table_bytes, uint64_t *rec_index, uint32_t *rows, uint64_t rows_cap,
+                                        uint64_t *n_rows, uint64_t *sample_table, uint64_t sample_cap,
+                                        uint64_t *n_samples, uint64_t *err_record);
+int vcfc_genotype_counts_regions_file(vcfc_ctx *ctx, const char *in_vcfc, const char *variants_tsv,
+                                      const char *samples_tsv, const uint8_t *table, uint64_t table_bytes);
+
 /* ---- sparse layout: sparsify_file (reference src/sparse.cpp:290-580) -------
  * Record i of the .vcfc goes to data_start + (300e6 + POS_i) * 16384
  * (compute_sparse_offset, src/sparse.cpp:18-51) behind a 16-byte prefix

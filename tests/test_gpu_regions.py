@@ -1,0 +1,286 @@
+"""GPU parity for region-list queries (query-regions, query-samples-regions,
+genotype-counts-regions): table bytes, flags, error word, status
+and output bytes against the Python restatement (regions_cases.py, pinned to
+the reference CLI by test_regions_emu.py) through the C ABI (libvcfc.so), the
+device entry on torch tensors and the CLI (build/main); the invariant -- set
+flags == OR of vcfc_query_match_device's flags -- on the device; and the
+golden pin to the reference's own per-region output."""
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+import pytest
+
+import golden_io as G
+import regions_cases as RC
+import subset_cases as SC
+
+pytestmark = pytest.mark.gpu
+REPO = G.REPO
+sys.path.insert(0, os.path.join(REPO, "vcf-compression_amd"))
+MAIN = os.path.join(REPO, "build", "main")
+OK, E_ARG, E_FORMAT = RC.OK, RC.E_ARG, RC.E_FORMAT
+DEV = "cuda:0"
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    import torch   # before libvcfc: one HIP runtime in the process
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    import vcfc
+    c = vcfc.Context(0)
+    yield c
+    c.close()
+
+
+def build(text):
+    import vcfc
+    try:
+        return vcfc.regions_build(text)
+    except ValueError as e:
+        raise RC.RegionError(int(str(e).split("line ")[1].split(":")[0]))
+
+
+def to_device(body, rec):
+    import torch
+    d_in = torch.from_numpy(np.frombuffer(body + bytes(64), dtype=np.uint8).copy()).to(DEV)
+    d_rec = torch.from_numpy(np.array(rec, dtype=np.uint64).view(np.int64)).to(DEV)
+    return d_in, d_rec
+
+
+def device_table(table):
+    """The table uploaded into a workspace with a canary behind it."""
+    import torch
+    import vcfc
+    wsb = vcfc.regions_workspace_size(len(table))
+    ws = torch.full((wsb + 64,), 0xCD, dtype=torch.uint8, device=DEV)
+    assert vcfc.regions_upload(table, ws.data_ptr(), wsb, torch.cuda.current_stream().cuda_stream) == OK
+    return ws, wsb
+
+
+def device_flags(d_in, d_rec, n, ws, wsb, calls=2):
+    """vcfc_regions_match_device, `calls` times on one workspace: the flags
+    and error word tensors; the canaries behind the flags and the workspace
+    checked."""
+    import torch
+    import vcfc
+    flag = torch.full((n + 64,), 0xEE, dtype=torch.uint8, device=DEV)
+    err = torch.zeros(1, dtype=torch.int64, device=DEV)
+    for _ in range(calls):
+        st = vcfc.regions_match_device(d_in.data_ptr(), d_rec.data_ptr(), n, ws.data_ptr(), wsb, flag.data_ptr(),
+                                       err.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        assert st == OK
+    torch.cuda.synchronize()
+    assert bool((flag[n:] == 0xEE).all()) and bool((ws[wsb:] == 0xCD).all()), "bytes written past the flags / the workspace"
+    return flag[:n], err
+
+
+def flags(body, rec, table):
+    d_in, d_rec = to_device(body, rec)
+    ws, wsb = device_table(table)
+    f, err = device_flags(d_in, d_rec, len(rec) - 1, ws, wsb)
+    return [int(x) for x in f.cpu().tolist()], int(err.cpu().numpy().view(np.uint64)[0])
+
+
+def single_device(d_in, d_rec, n, q):
+    import torch
+    import vcfc
+    d_ref = torch.tensor(list(q[0]) + [0], dtype=torch.uint8, device=DEV)
+    flag = torch.full((n + 64,), 0xEE, dtype=torch.uint8, device=DEV)
+    err = torch.zeros(1, dtype=torch.int64, device=DEV)
+    st = vcfc.query_match_device(d_in.data_ptr(), d_rec.data_ptr(), n, d_ref.data_ptr(), len(q[0]), q[1], q[2], q[3],
+                                 flag.data_ptr(), err.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    assert st == OK
+    return flag[:n], err
+
+
+def single(body, rec, q):
+    d_in, d_rec = to_device(body, rec)
+    f, err = single_device(d_in, d_rec, len(rec) - 1, q)
+    return [int(x) for x in f.cpu().tolist()], int(err.cpu().numpy().view(np.uint64)[0])
+
+
+@pytest.fixture(scope="module")
+def qry(ctx):
+    return lambda data, text: ctx.query_regions_buffer(data, build(text))
+
+
+@pytest.fixture(scope="module")
+def qsam(ctx):
+    return lambda data, text, cols: ctx.query_samples_regions_buffer(data, build(text), cols)
+
+
+@pytest.fixture(scope="module")
+def cnt(ctx):
+    def run(data, text):
+        st, idx, rows, tab = ctx.genotype_counts_regions_buffer(data, build(text))
+        return st, [int(x) for x in idx], rows.tolist(), None if tab is None else tab.tolist(), ctx.last_counts_record
+    return run
+
+
+# ---- the table ----------------------------------------------------------------------
+
+def test_region_text_and_exports():
+    import vcfc
+    RC.check_text(build)
+    for name in ("vcfc_regions_build", "vcfc_regions_workspace_size", "vcfc_regions_upload", "vcfc_regions_match_device",
+                 "vcfc_query_regions_buffer", "vcfc_query_regions_file", "vcfc_query_samples_regions_buffer",
+                 "vcfc_query_samples_regions_file", "vcfc_genotype_counts_regions_buffer",
+                 "vcfc_genotype_counts_regions_file"):
+        assert name in vcfc.EXPORTS and hasattr(vcfc.lib(), name), name
+    with pytest.raises(ValueError, match="Failed to parse region at line 2: 1:5"):
+        vcfc.regions_build(b"1:100-200\n1:5\n")
+
+
+def test_upload_refuses_corrupt_tables():
+    import torch
+    import vcfc
+    table = bytearray(build(b"1:10-19\n1:30-40\n2:5-6\nchrX\n"))
+    wsb = vcfc.regions_workspace_size(len(table))
+    ws = torch.full((wsb + 64,), 0xCD, dtype=torch.uint8, device=DEV)
+    o_st = int(np.frombuffer(bytes(table[:40]), dtype=np.uint32)[5])
+    bad = {"magic": bytes([0x58]) + bytes(table[1:]), "truncated": bytes(table[:-8]), "empty": b"",
+           "offset past the end": bytes(table[:20]) + np.uint32(len(table)).tobytes() + bytes(table[24:]),
+           "unsorted starts": bytes(table[:o_st + 8]) + bytes(8) + bytes(table[o_st + 16:])}
+    for why, t in bad.items():
+        assert vcfc.regions_upload(t, ws.data_ptr(), wsb) == E_ARG, why
+    assert vcfc.regions_upload(bytes(table), ws.data_ptr(), wsb - 256) == E_ARG
+    torch.cuda.synchronize()
+    assert bool((ws == 0xCD).all()), "a refused table was copied"
+    assert vcfc.regions_upload(bytes(table), ws.data_ptr(), wsb) == OK
+
+
+# ---- flags and error word ----------------------------------------------------------------
+
+def test_sets_on_query_files():
+    RC.check_sets(flags, build, 1)
+
+
+def test_invariant_or_of_single_region_flags():
+    RC.check_invariant(flags, single, build, 1)
+
+
+def test_table_shapes_and_record_counts():
+    RC.check_shapes(flags, build)
+
+
+def test_invariant_on_a_device_batch():
+    """4096 x 2504 freshly encoded rows against a 64-region set: the set's
+    flags == the OR of vcfc_query_match_device's flags, on the device."""
+    import torch
+    import vcfc
+    import workload
+    n, S = 4096, 2504
+    rows = workload.DeviceRows(torch, vcfc, n, S, 1, seed=5, device=DEV)
+    cap, wsb = vcfc.encode_bound(n, rows.line_bytes), vcfc.workspace_size(n, rows.line_bytes)
+    ews = torch.empty(wsb, dtype=torch.uint8, device=DEV)
+    recs = torch.empty(cap, dtype=torch.uint8, device=DEV)
+    rec = torch.empty(n + 1, dtype=torch.int64, device=DEV)
+    err = torch.empty(1, dtype=torch.int64, device=DEV)
+    stream = torch.cuda.current_stream().cuda_stream
+    vcfc.encode_rows_device(rows.buf.data_ptr(), rows.line_off.data_ptr(), rows.line_len.data_ptr(), n, rows.line_bytes,
+                            recs.data_ptr(), cap, rec.data_ptr(), ews.data_ptr(), wsb, err.data_ptr(), stream)
+    torch.cuda.synchronize()
+    assert int(err.item()) == -1
+    pos = [int(p) for p in rows.pos]
+    chrom = rows.chrom.encode()
+    regions = []
+    for k in range(60):   # 60 windows of 20 rows every 64 rows, some overlapping their neighbour
+        lo = pos[64 * k + 7]
+        regions.append((chrom, lo, pos[64 * k + 26 + (50 if k % 9 == 0 else 0)]))
+    regions += [(chrom + b"x", 0, RC.U64), (b"", pos[4000], pos[4000]), (chrom, pos[4090] + 1, pos[4090]),
+                (chrom, pos[-1], RC.U64)]
+    assert len(regions) == 64
+    ws, wsb_t = device_table(build(RC.text_of(regions)))
+    got, gerr = device_flags(recs, rec, n, ws, wsb_t)
+    acc = torch.zeros(n, dtype=torch.uint8, device=DEV)
+    for q in regions:
+        f, e = single_device(recs, rec, n, (q[0], True, q[1], q[2]))
+        acc |= f
+        assert int(e.item()) == -1
+    torch.cuda.synchronize()
+    assert int(gerr.item()) == -1 and bool(torch.equal(got, acc))
+    assert 1000 < int(got.sum().item()) < n
+
+
+# ---- the three drivers, the CLI, the golden pin ---------------------------------------------
+
+def test_drivers(qry, qsam, cnt):
+    assert RC.check_drivers(qry, qsam, cnt, 1) == (8, 16)
+
+
+def test_driver_arguments(ctx, qry, qsam, cnt):
+    name, data = SC.query_files(1)[0]
+    for cols in ([], [40], [2, 2]):
+        assert qsam(data, RC.SETS["A"], cols) == (E_ARG, b"")
+    assert qry(data[1:], RC.SETS["A"]) == (E_FORMAT, b"")
+    assert qry(data, b"") == (OK, b"") and cnt(data, b"# none\n")[:3] == (OK, [], [])
+    table = build(RC.SETS["A"])
+    assert ctx.query_regions_buffer(data, b"VCRG" + bytes(len(table) - 4)) == (E_ARG, b"")
+    # a short buffer: VCFC_E_NOSPACE and the size needed (the wrapper then retries with it)
+    want = RC.query_regions(data, RC.parse_text(RC.SETS["A"]))
+    assert len(want[1]) > 0 and ctx.query_regions_buffer(data, table, cap=5) == want
+    assert ctx.query_samples_regions_buffer(data, table, [1], cap=5) == RC.query_samples_regions(data, RC.parse_text(RC.SETS["A"]), [1])
+
+
+def test_reference_cli_golden(qry):
+    RC.check_golden(qry)
+
+
+def test_cli(ctx):
+    def cli(argv):
+        return subprocess.run([MAIN] + argv, capture_output=True, timeout=300)
+    g = RC.golden()
+    enc = G.gz(g["file"])
+    vcf = G.gz(g["file"].replace(".vcfc", ".vcf"))
+    names = vcf[vcf.index(b"#CHROM"):].split(b"\n", 1)[0].split(b"\t")[9:]
+    cols = [77, 3, 50]
+    pick = b",".join(names[c] for c in cols).decode()
+    bed = b"# targets\ntrack name=t\n1\t9999\t10100\textra\n1:15000-15999\r\n1:15500-16500\n2\n1\t20001\t20002"
+    with tempfile.TemporaryDirectory() as d:
+        src, reg, vt, stx = (os.path.join(d, x) for x in ("t.vcfc", "r.bed", "v.tsv", "s.tsv"))
+        with open(src, "wb") as f:
+            f.write(enc)
+        with open(reg, "wb") as f:
+            f.write(bed)
+        table = build(bed)
+        r = cli(["query-regions", src, reg])
+        want = ctx.query_regions_buffer(enc, table)
+        assert r.returncode == 0 and want[0] == OK and r.stdout == want[1] and want[1].count(b"\n") == 51 + 751 + 1, r.stderr
+        r = cli(["query-samples-regions", src, reg, pick])
+        assert r.returncode == 0 and r.stdout == ctx.query_samples_regions_buffer(enc, table, cols)[1] == SC.cut_vcf(want[1], cols)
+        r = cli(["genotype-counts-regions", src, vt, stx, reg])
+        assert r.returncode == 0, r.stderr
+        vt2, st2 = os.path.join(d, "v2.tsv"), os.path.join(d, "s2.tsv")
+        ctx.genotype_counts_regions_file(src, vt2, st2, table)
+        assert open(vt, "rb").read() == open(vt2, "rb").read() and open(stx, "rb").read() == open(st2, "rb").read()
+        assert open(vt, "rb").read().count(b"\n") == 1 + 803
+        # a region line that does not parse: the message, exit 1, before the input is opened
+        with open(reg, "wb") as f:
+            f.write(b"1:100-200\n# c\n1\t5\tx\n")
+        for argv in (["query-regions", os.path.join(d, "absent.vcfc"), reg], ["query-samples-regions", src, reg, pick],
+                     ["genotype-counts-regions", src, vt, stx, reg]):
+            r = cli(argv)
+            assert (r.returncode, r.stdout) == (1, b"Failed to parse region at line 3: 1\t5\tx\n"), argv
+        r = cli(["query-regions", src, os.path.join(d, "absent.bed")])
+        assert r.returncode == 1 and r.stdout == b"" and b"absent.bed" in r.stderr
+        for argv in (["query-regions", src], ["query-samples-regions", src, reg], ["genotype-counts-regions", src, vt, stx]):
+            r = cli(argv)
+            assert r.returncode == 1
+            for l in (b"./main query-regions <input_file> <regions-file>\n",
+                      b"./main query-samples-regions <input_file> <regions-file> <name>[,<name>...]\n",
+                      b"./main genotype-counts-regions <input_file> <variants.tsv> <samples.tsv> <regions-file>\n",
+                      b"./main [query|sparse-query] <input_file> <ref>[:<start>-<end>]\n"):
+                assert l in r.stderr
+        # a file that stops mid-way: exit 134 with the lines before the stop written
+        name, bad = next(x for x in SC.query_files(1) if x[0] == "pos_bad17")
+        with open(src, "wb") as f:
+            f.write(bad)
+        with open(reg, "wb") as f:
+            f.write(RC.SETS["B"])
+        r = cli(["query-regions", src, reg])
+        want = RC.query_regions(bad, RC.parse_text(RC.SETS["B"]))
+        assert want[0] == E_FORMAT and 0 < len(want[1]) and r.returncode == 134 and r.stdout == want[1]
+        assert b"VcfValidationError" in r.stderr

@@ -8,7 +8,10 @@
 // `main decompress-samples <in> <out> <names>` and
 // `main query-samples <in> <query> <names>`, and the counts:
 // `main genotype-counts <in> <variants.tsv> <samples.tsv> [<query>]`
-// (DESIGN.md §4j).  Data lines are
+// (DESIGN.md §4j), and the region lists: `main query-regions <in> <regions>`,
+// `main query-samples-regions <in> <regions> <names>` and
+// `main genotype-counts-regions <in> <variants.tsv> <samples.tsv> <regions>`
+// (DESIGN.md §4k).  Data lines are
 // encoded on the GPU through libvcfc.so.  Error messages mirror the
 // reference's exceptions (which terminate the reference process).
 #include <cerrno>
@@ -34,7 +37,10 @@ static int usage() {
                     "./main gap-analysis <compressed-filename>\n"
                     "./main decompress-samples <input_file> <output_file> <name>[,<name>...]\n"
                     "./main query-samples <input_file> <ref>[:<start>-<end>] <name>[,<name>...]\n"
-                    "./main genotype-counts <input_file> <variants.tsv> <samples.tsv> [<ref>[:<start>-<end>]]\n");
+                    "./main genotype-counts <input_file> <variants.tsv> <samples.tsv> [<ref>[:<start>-<end>]]\n"
+                    "./main query-regions <input_file> <regions-file>\n"
+                    "./main query-samples-regions <input_file> <regions-file> <name>[,<name>...]\n"
+                    "./main genotype-counts-regions <input_file> <variants.tsv> <samples.tsv> <regions-file>\n");
     return 1;
 }
 
@@ -74,6 +80,47 @@ static int resolve_samples(const char *path, const std::string &names, std::vect
     }
     cols.resize(st == VCFC_OK ? n_cols : 0);
     return st;
+}
+
+// The region table of a regions file (BED or <ref>[:<start>-<end>] lines).
+// 0: table filled; 1: a message was printed (the file cannot be read, or a
+// line does not parse).
+static int load_regions(const char *path, std::vector<uint8_t> &table) {
+    std::string text;
+    FILE *f = fopen(path, "rb");
+    if (!f) {
+        fprintf(stderr, "Cannot read regions file: %s\n", path);
+        return 1;
+    }
+    char buf[1 << 16];
+    size_t r;
+    while ((r = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, r);
+    const bool bad = ferror(f) != 0;
+    fclose(f);
+    if (bad) {
+        fprintf(stderr, "Cannot read regions file: %s\n", path);
+        return 1;
+    }
+    uint64_t bytes = 0, n_regions = 0, bad_line = 0;
+    int st = vcfc_regions_build(text.data(), text.size(), nullptr, 0, &bytes, &n_regions, &bad_line);
+    if (st == VCFC_E_NOSPACE) {
+        table.resize(bytes);
+        st = vcfc_regions_build(text.data(), text.size(), table.data(), table.size(), &bytes, &n_regions, &bad_line);
+    }
+    if (st == VCFC_E_ARG && bad_line) {
+        size_t a = 0;
+        for (uint64_t l = 1; l < bad_line; l++) a = text.find('\n', a) + 1;
+        size_t e = text.find('\n', a);
+        if (e == std::string::npos) e = text.size();
+        else if (e > a && text[e - 1] == '\r') e--;
+        printf("Failed to parse region at line %llu: %s\n", (unsigned long long)bad_line, text.substr(a, e - a).c_str());
+        return 1;
+    }
+    if (st != VCFC_OK) {
+        fprintf(stderr, "Cannot build the region table: %s\n", vcfc_strerror(st));
+        return 1;
+    }
+    return 0;
 }
 
 static bool file_exists(const char *p) {
@@ -498,6 +545,45 @@ int main(int argc, char **argv) {
         }
         if (st != VCFC_OK) {
             fprintf(stderr, "Error in genotype-counts of file: %s\n", vcfc_strerror(st));
+            return 1;
+        }
+        return 0;
+    }
+    if (action == "query-regions" || action == "query-samples-regions" || action == "genotype-counts-regions") {
+        // no reference counterpart: `query`, `query-samples` and `genotype-counts` over a region list
+        const bool samples = action == "query-samples-regions", counts = action == "genotype-counts-regions";
+        if (argc < (counts ? 6 : samples ? 5 : 4)) return usage();
+        std::vector<uint8_t> table;
+        if (load_regions(argv[counts ? 5 : 3], table)) return 1;   // before the input is opened
+        if (!file_exists(argv[2])) printf("Input file does not exist: %s\n", argv[2]);
+        if (counts && (std::string(argv[2]) == argv[3] || std::string(argv[2]) == argv[4] || std::string(argv[3]) == argv[4])) {
+            fprintf(stderr, "terminate called after throwing an instance of 'std::runtime_error'\n"
+                            "  what():  input and output file are the same\n");
+            return 134;
+        }
+        std::vector<uint32_t> cols;
+        int st = samples ? resolve_samples(argv[2], argv[4], cols) : VCFC_OK;
+        if (st == 1) return 1;   // unknown / duplicate name: message printed, nothing written
+        if (st == VCFC_OK) {
+            vcfc_ctx *ctx = nullptr;
+            st = vcfc_ctx_create(0, &ctx);
+            if (st != VCFC_OK) {
+                fprintf(stderr, "vcfc: %s\n", vcfc_strerror(st));
+                return 1;
+            }
+            fflush(stdout);
+            if (counts) st = vcfc_genotype_counts_regions_file(ctx, argv[2], argv[3], argv[4], table.data(), table.size());
+            else if (samples) st = vcfc_query_samples_regions_file(ctx, argv[2], table.data(), table.size(), cols.data(), cols.size(), 1);
+            else st = vcfc_query_regions_file(ctx, argv[2], table.data(), table.size(), 1);
+            vcfc_ctx_destroy(ctx);
+        }
+        if (st == VCFC_E_FORMAT) {
+            fprintf(stderr, "terminate called after throwing an instance of 'VcfValidationError'\n"
+                            "  what():  %s\n", vcfc_strerror(st));
+            return 134;
+        }
+        if (st != VCFC_OK) {
+            fprintf(stderr, "Error in %s of file: %s\n", counts ? "genotype-counts" : "decompression", vcfc_strerror(st));
             return 1;
         }
         return 0;

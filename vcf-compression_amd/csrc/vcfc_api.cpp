@@ -25,6 +25,7 @@
 #include "vcfc_sparse_index_driver.h"
 #include "vcfc_subset_driver.h"
 #include "vcfc_counts_driver.h"
+#include "vcfc_regions_driver.h"
 
 hipError_t vcfc_sparse_plan_launch(const uint8_t *recs, const uint64_t *rec_off, uint64_t n, uint64_t data_start,
                                    uint64_t *file_off, uint8_t *prefix, uint64_t *status, hipStream_t s);
@@ -882,44 +883,12 @@ int vcfc_decompress_file(vcfc_ctx *c, const char *in_path, const char *out_path)
 // ---- range query: query_compressed_file, reference
 // src/main.cpp:3777-3929 ----------------------------------------------------
 
-// parse_coordinate_string (src/main.cpp:3993-4026) with str_to_uint64
-// (src/utils.cpp:152-165: strtoul over the whole string; "" parses as 0)
-static bool str_to_u64(const char *s, uint64_t n, uint64_t *out) {
-    if (n == 0) { *out = 0; return true; }
-    uint64_t i = 0;
-    while (i < n && (s[i] == ' ' || (s[i] >= '\t' && s[i] <= '\r'))) i++;
-    bool neg = false;
-    if (i < n && (s[i] == '+' || s[i] == '-')) { neg = s[i] == '-'; i++; }
-    if (i >= n || s[i] < '0' || s[i] > '9') return false;
-    uint64_t v = 0;
-    bool ovf = false;
-    for (; i < n && s[i] >= '0' && s[i] <= '9'; i++) {
-        const uint64_t d = (uint64_t)(s[i] - '0');
-        ovf = ovf || v > (UINT64_MAX - d) / 10;
-        v = v * 10 + d;
-    }
-    if (i != n) return false;
-    *out = ovf ? UINT64_MAX : (neg ? 0 - v : v);
-    return true;
-}
-
+// parse_coordinate_string (src/main.cpp:3993-4026): vcfc_regions_driver.h,
+// where the region text parser shares it
 int vcfc_parse_query(const char *q, uint64_t q_len, uint64_t *ref_len, int *has_range, uint64_t *start,
                      uint64_t *end) {
     if ((!q && q_len) || !ref_len || !has_range || !start || !end) return VCFC_E_ARG;
-    const char *colon = q_len ? static_cast<const char *>(memchr(q, ':', q_len)) : nullptr;
-    if (!colon) {
-        *ref_len = q_len; *has_range = 0; *start = *end = 0;
-        return 0;
-    }
-    const uint64_t ci = (uint64_t)(colon - q);
-    const char *dash = static_cast<const char *>(memchr(q + ci + 1, '-', q_len - ci - 1));
-    if (!dash) return 1;
-    const uint64_t di = (uint64_t)(dash - q);
-    if (!str_to_u64(q + ci + 1, di - ci - 1, start)) return 2;
-    if (!str_to_u64(q + di + 1, q_len - di - 1, end)) return 3;
-    *ref_len = ci;
-    *has_range = 1;
-    return 0;
+    return vcfc_reg::parse_query(q, q_len, ref_len, has_range, start, end);
 }
 
 int vcfc_query_buffer(vcfc_ctx *c, const uint8_t *in, uint64_t n, const char *ref, uint64_t ref_len, int has_range,
@@ -1467,6 +1436,56 @@ int vcfc_genotype_counts_device(const uint8_t *d_in, uint64_t in_bytes, const ui
                                    d_err, static_cast<hipStream_t>(stream));
 }
 
+namespace {
+// what the two genotype-counts buffer entries hand back from a Result
+int counts_to_caller(int st, const vcfc_cnt::Result &R, uint64_t S, uint64_t *rec_index, uint32_t *rows, uint64_t rows_cap,
+                     uint64_t *n_rows, uint64_t *sample_table, uint64_t sample_cap, uint64_t *n_samples,
+                     uint64_t *err_record) {
+    if (st != VCFC_OK && st != VCFC_E_FORMAT) return st;
+    *n_rows = R.index.size();
+    *n_samples = st == VCFC_OK ? S : 0;
+    *err_record = R.err_record;
+    if (*n_rows > rows_cap || *n_samples > sample_cap) return VCFC_E_NOSPACE;
+    if (*n_rows) {
+        memcpy(rec_index, R.index.data(), 8 * R.index.size());
+        memcpy(rows, R.rows.data(), 4 * R.rows.size());
+    }
+    if (st == VCFC_OK) memcpy(sample_table, R.samples.data(), 8 * R.samples.size());
+    return st;
+}
+
+// the two files of a genotype-counts file entry; run(f, R, &data_off, &S) counts
+int counts_to_files(const char *in_path, const char *variants_path, const char *samples_path,
+                    const std::function<int(const MappedFile &, vcfc_cnt::Result &, uint64_t *, uint64_t *)> &run) {
+    const int vfd = open(variants_path, O_CREAT | O_TRUNC | O_WRONLY, 0644);
+    if (vfd < 0) return VCFC_E_IO;
+    const int sfd = open(samples_path, O_CREAT | O_TRUNC | O_WRONLY, 0644);
+    if (sfd < 0) {
+        close(vfd);
+        return VCFC_E_IO;
+    }
+    MappedFile f;
+    int st = f.open_ro(in_path);
+    if (!st) {
+        vcfc_cnt::Result R;
+        uint64_t data_off = 0, S = 0;
+        st = run(f, R, &data_off, &S);
+        if (data_off && S && (st == VCFC_OK || st == VCFC_E_FORMAT)) {   // past the header
+            std::vector<uint8_t> text;
+            vcfc_cnt::render_variants(f.p + data_off, R, text);
+            if (write_all_at(vfd, text.data(), text.size(), 0)) st = VCFC_E_IO;
+            if (st == VCFC_OK) {
+                vcfc_cnt::render_samples(f.p, data_off, S, R, text);
+                if (write_all_at(sfd, text.data(), text.size(), 0)) st = VCFC_E_IO;
+            }
+        }
+    }
+    if (close(vfd) != 0 && !st) st = VCFC_E_IO;
+    if (close(sfd) != 0 && !st) st = VCFC_E_IO;
+    return st;
+}
+}  // namespace
+
 int vcfc_genotype_counts_buffer(vcfc_ctx *c, const uint8_t *in, uint64_t n, int has_query, const char *ref,
                                 uint64_t ref_len, int has_range, uint64_t start, uint64_t end, uint64_t *rec_index,
                                 uint32_t *rows, uint64_t rows_cap, uint64_t *n_rows, uint64_t *sample_table,
@@ -1482,17 +1501,7 @@ int vcfc_genotype_counts_buffer(vcfc_ctx *c, const uint8_t *in, uint64_t n, int 
     uint64_t data_off = 0, S = 0;
     CtxDecodeBuffers B(c);
     const int st = vcfc_cnt::counts_file(in, n, has_query ? &q : nullptr, B, c->stream, R, &data_off, &S);
-    if (st != VCFC_OK && st != VCFC_E_FORMAT) return st;
-    *n_rows = R.index.size();
-    *n_samples = st == VCFC_OK ? S : 0;
-    *err_record = R.err_record;
-    if (*n_rows > rows_cap || *n_samples > sample_cap) return VCFC_E_NOSPACE;
-    if (*n_rows) {
-        memcpy(rec_index, R.index.data(), 8 * R.index.size());
-        memcpy(rows, R.rows.data(), 4 * R.rows.size());
-    }
-    if (st == VCFC_OK) memcpy(sample_table, R.samples.data(), 8 * R.samples.size());
-    return st;
+    return counts_to_caller(st, R, S, rec_index, rows, rows_cap, n_rows, sample_table, sample_cap, n_samples, err_record);
 }
 
 int vcfc_genotype_counts_file(vcfc_ctx *c, const char *in_path, const char *variants_path, const char *samples_path,
@@ -1500,34 +1509,159 @@ int vcfc_genotype_counts_file(vcfc_ctx *c, const char *in_path, const char *vari
                               uint64_t end) {
     if (!c || !in_path || !variants_path || !samples_path || (has_query && !ref && ref_len)) return VCFC_E_ARG;
     if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
-    const int vfd = open(variants_path, O_CREAT | O_TRUNC | O_WRONLY, 0644);
-    if (vfd < 0) return VCFC_E_IO;
-    const int sfd = open(samples_path, O_CREAT | O_TRUNC | O_WRONLY, 0644);
-    if (sfd < 0) {
-        close(vfd);
-        return VCFC_E_IO;
+    const vcfc_cnt::Query q{reinterpret_cast<const uint8_t *>(ref), ref_len, has_range, start, end};
+    return counts_to_files(in_path, variants_path, samples_path,
+                           [&](const MappedFile &f, vcfc_cnt::Result &R, uint64_t *data_off, uint64_t *S) {
+                               CtxDecodeBuffers B(c);
+                               return vcfc_cnt::counts_file(f.p, f.n, has_query ? &q : nullptr, B, c->stream, R, data_off, S);
+                           });
+}
+
+// ---- region-list queries; drivers in vcfc_regions_driver.h ----
+
+int vcfc_regions_build(const char *text, uint64_t len, uint8_t *table, uint64_t table_cap, uint64_t *table_bytes,
+                       uint64_t *n_regions, uint64_t *bad_line) {
+    if ((!text && len) || (!table && table_cap) || !table_bytes || !n_regions || !bad_line) return VCFC_E_ARG;
+    return vcfc_reg::regions_build(text, len, table, table_cap, table_bytes, n_regions, bad_line);
+}
+
+uint64_t vcfc_regions_workspace_size(uint64_t table_bytes) { return vcfc_reg::regions_workspace_size(table_bytes); }
+
+int vcfc_regions_upload(const uint8_t *table, uint64_t table_bytes, void *d_ws, uint64_t ws_bytes, void *stream) {
+    return vcfc_reg::regions_upload(table, table_bytes, d_ws, ws_bytes, static_cast<hipStream_t>(stream));
+}
+
+int vcfc_regions_match_device(const uint8_t *d_in, const uint64_t *d_rec_start, uint64_t n, const void *d_ws,
+                              uint64_t ws_bytes, uint8_t *d_flag, uint64_t *d_err, void *stream) {
+    return vcfc_reg::regions_match_device(d_in, d_rec_start, n, d_ws, ws_bytes, d_flag, d_err,
+                                          static_cast<hipStream_t>(stream));
+}
+
+namespace {
+// the sink of a buffer call: counts every byte, copies while they fit
+struct BufferSink {
+    uint8_t *out;
+    uint64_t cap, o = 0;
+    bool fits = true;
+    bool operator()(const uint8_t *p, uint64_t k) {
+        if (fits && o + k <= cap) memcpy(out + o, p, k);
+        else fits = false;
+        o += k;
+        return true;
     }
+};
+// the sink of a call that writes to a descriptor
+struct FdSink {
+    int fd;
+    bool operator()(const uint8_t *p, uint64_t k) const {
+        while (k) {
+            const ssize_t w = write(fd, p, std::min<uint64_t>(k, 1ull << 30));
+            if (w <= 0) return false;
+            p += w;
+            k -= (uint64_t)w;
+        }
+        return true;
+    }
+};
+}  // namespace
+
+int vcfc_query_regions_buffer(vcfc_ctx *c, const uint8_t *in, uint64_t n, const uint8_t *table, uint64_t table_bytes,
+                              uint8_t *out, uint64_t out_cap, uint64_t *out_len) {
+    if (!c || (!in && n) || (!out && out_cap) || !out_len || !vcfc_reg::regions_validate(table, table_bytes))
+        return VCFC_E_ARG;
+    *out_len = 0;
+    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
+    uint64_t data_off = 0, S = 0;
+    int st = parse_vcfc_header(in, n, &data_off, &S);
+    if (st) return st;
+    BufferSink bs{out, out_cap};
+    const uint8_t *d_table = nullptr;
+    CtxDecodeBuffers B(c);
+    st = vcfc_dec::query_regions_section(in + data_off, n - data_off, S, vcfc_reg::regions_step(table, table_bytes, &d_table),
+                                         B, c->stream, std::ref(bs));
+    *out_len = bs.o;
+    return bs.fits ? st : VCFC_E_NOSPACE;
+}
+
+int vcfc_query_regions_file(vcfc_ctx *c, const char *in_path, const uint8_t *table, uint64_t table_bytes, int out_fd) {
+    if (!c || !in_path || out_fd < 0 || !vcfc_reg::regions_validate(table, table_bytes)) return VCFC_E_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
     MappedFile f;
     int st = f.open_ro(in_path);
-    if (!st) {
-        const vcfc_cnt::Query q{reinterpret_cast<const uint8_t *>(ref), ref_len, has_range, start, end};
-        vcfc_cnt::Result R;
-        uint64_t data_off = 0, S = 0;
-        CtxDecodeBuffers B(c);
-        st = vcfc_cnt::counts_file(f.p, f.n, has_query ? &q : nullptr, B, c->stream, R, &data_off, &S);
-        if (data_off && S && (st == VCFC_OK || st == VCFC_E_FORMAT)) {   // past the header
-            std::vector<uint8_t> text;
-            vcfc_cnt::render_variants(f.p + data_off, R, text);
-            if (write_all_at(vfd, text.data(), text.size(), 0)) st = VCFC_E_IO;
-            if (st == VCFC_OK) {
-                vcfc_cnt::render_samples(f.p, data_off, S, R, text);
-                if (write_all_at(sfd, text.data(), text.size(), 0)) st = VCFC_E_IO;
-            }
-        }
-    }
-    if (close(vfd) != 0 && !st) st = VCFC_E_IO;
-    if (close(sfd) != 0 && !st) st = VCFC_E_IO;
-    return st;
+    if (st) return st;
+    uint64_t data_off = 0, S = 0;
+    if ((st = parse_vcfc_header(f.p, f.n, &data_off, &S))) return st;
+    const uint8_t *d_table = nullptr;
+    CtxDecodeBuffers B(c);
+    return vcfc_dec::query_regions_section(f.p + data_off, f.n - data_off, S,
+                                           vcfc_reg::regions_step(table, table_bytes, &d_table), B, c->stream, FdSink{out_fd});
+}
+
+int vcfc_query_samples_regions_buffer(vcfc_ctx *c, const uint8_t *in, uint64_t n, const uint8_t *table,
+                                      uint64_t table_bytes, const uint32_t *cols, uint64_t n_cols, uint8_t *out,
+                                      uint64_t out_cap, uint64_t *out_len) {
+    if (!c || (!in && n) || (!out && out_cap) || !out_len || !vcfc_reg::regions_validate(table, table_bytes))
+        return VCFC_E_ARG;
+    *out_len = 0;
+    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
+    SubsetCall sc;
+    int st = sc.prepare(in, n, cols, n_cols);
+    if (st) return st;
+    BufferSink bs{out, out_cap};
+    const uint8_t *d_table = nullptr;
+    CtxDecodeBuffers B(c);
+    st = vcfc_sub::matched_section(in + sc.data_off, n - sc.data_off, sc.S, sc.csort, sc.rank,
+                                   vcfc_reg::regions_step(table, table_bytes, &d_table), B, c->stream, std::ref(bs));
+    *out_len = bs.o;
+    return bs.fits ? st : VCFC_E_NOSPACE;
+}
+
+int vcfc_query_samples_regions_file(vcfc_ctx *c, const char *in_path, const uint8_t *table, uint64_t table_bytes,
+                                    const uint32_t *cols, uint64_t n_cols, int out_fd) {
+    if (!c || !in_path || out_fd < 0 || !vcfc_reg::regions_validate(table, table_bytes)) return VCFC_E_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
+    MappedFile f;
+    int st = f.open_ro(in_path);
+    if (st) return st;
+    SubsetCall sc;
+    if ((st = sc.prepare(f.p, f.n, cols, n_cols))) return st;
+    const uint8_t *d_table = nullptr;
+    CtxDecodeBuffers B(c);
+    return vcfc_sub::matched_section(f.p + sc.data_off, f.n - sc.data_off, sc.S, sc.csort, sc.rank,
+                                     vcfc_reg::regions_step(table, table_bytes, &d_table), B, c->stream, FdSink{out_fd});
+}
+
+int vcfc_genotype_counts_regions_buffer(vcfc_ctx *c, const uint8_t *in, uint64_t n, const uint8_t *table,
+                                        uint64_t table_bytes, uint64_t *rec_index, uint32_t *rows, uint64_t rows_cap,
+                                        uint64_t *n_rows, uint64_t *sample_table, uint64_t sample_cap, uint64_t *n_samples,
+                                        uint64_t *err_record) {
+    if (!c || (!in && n) || ((!rec_index || !rows) && rows_cap) || (!sample_table && sample_cap) || !n_rows ||
+        !n_samples || !err_record || !vcfc_reg::regions_validate(table, table_bytes))
+        return VCFC_E_ARG;
+    *n_rows = *n_samples = 0;
+    *err_record = ~0ull;
+    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
+    const uint8_t *d_table = nullptr;
+    const vcfc_dec::MatchStep match = vcfc_reg::regions_step(table, table_bytes, &d_table);
+    vcfc_cnt::Result R;
+    uint64_t data_off = 0, S = 0;
+    CtxDecodeBuffers B(c);
+    const int st = vcfc_cnt::counts_file(in, n, &match, B, c->stream, R, &data_off, &S);
+    return counts_to_caller(st, R, S, rec_index, rows, rows_cap, n_rows, sample_table, sample_cap, n_samples, err_record);
+}
+
+int vcfc_genotype_counts_regions_file(vcfc_ctx *c, const char *in_path, const char *variants_path,
+                                      const char *samples_path, const uint8_t *table, uint64_t table_bytes) {
+    if (!c || !in_path || !variants_path || !samples_path || !vcfc_reg::regions_validate(table, table_bytes))
+        return VCFC_E_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
+    const uint8_t *d_table = nullptr;
+    const vcfc_dec::MatchStep match = vcfc_reg::regions_step(table, table_bytes, &d_table);
+    return counts_to_files(in_path, variants_path, samples_path,
+                           [&](const MappedFile &f, vcfc_cnt::Result &R, uint64_t *data_off, uint64_t *S) {
+                               CtxDecodeBuffers B(c);
+                               return vcfc_cnt::counts_file(f.p, f.n, &match, B, c->stream, R, data_off, S);
+                           });
 }
 
 int vcfc_query_match_device(const uint8_t *d_in, const uint64_t *d_rec_start, uint64_t n, const uint8_t *d_ref,

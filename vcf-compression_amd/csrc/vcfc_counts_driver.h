@@ -5,8 +5,9 @@
 //
 //   1. the header: S from the '#CHROM' line (ST_E_ARG for S == 0 or >= 2^30);
 //   2. hop the LEN headers on the host to find record starts;
-//   3. with a query, the range query's match step (its kernel and error word
-//      unchanged) flags the records to count;
+//   3. with a query, a match step (vcfc_dec::MatchStep: the range query's,
+//      kernel and error word unchanged, or a region table's)
+//      flags the records to count;
 //   4. the records in batches of rec_batch: one scan each gives the batch's
 //      rows and adds to the sample table, which stays on the device;
 //   5. ST_E_FORMAT at the first counted record that is not regular, at a match
@@ -69,11 +70,11 @@ inline int counts_device(const uint8_t *d_in, uint64_t in_bytes, const uint64_t 
 }
 
 // The data section of a .vcfc (host bytes h_in[0, n); uploaded here).  q ==
-// nullptr: every record is counted.
-inline int counts_section(const uint8_t *h_in, uint64_t n, uint64_t S, const Query *q, Buffers &B, hipStream_t s,
-                          Result &R, uint64_t rec_batch = 1ull << 22) {
+// nullptr: every record is counted; else the records the match step flags
+// (vcfc_dec::MatchStep: one region, or a region table).
+inline int counts_section(const uint8_t *h_in, uint64_t n, uint64_t S, const vcfc_dec::MatchStep *q, Buffers &B,
+                          hipStream_t s, Result &R, uint64_t rec_batch = 1ull << 22) {
     R = Result();
-    if (q && q->ref_len > 0xFFFFFFFFull) return ST_E_FORMAT;
     std::vector<uint64_t> rec;
     vcfc_dec::hop(h_in, n, rec);
     R.rec_start = rec;
@@ -90,16 +91,13 @@ inline int counts_section(const uint8_t *h_in, uint64_t n, uint64_t S, const Que
         if (!d_in || !d_rec) return ST_E_HIP;
         const uint8_t *d_flag = nullptr;
         if (q) {
-            const uint8_t *d_ref = vcfc_dec::upload(B, Buffers::QREF, q->ref, q->ref_len, s);
+            const bool ready = q->prepare(B, s);
             uint64_t *d_small = static_cast<uint64_t *>(B.get(Buffers::SMALL, 64));
             uint8_t *d_f = static_cast<uint8_t *>(B.get(Buffers::FLAG, nrec + 64));
-            if (!d_ref || !d_small || !d_f) return ST_E_HIP;
-            VcfcQuery vq;
-            vq.ref = d_ref; vq.ref_len = (uint32_t)q->ref_len; vq.has_range = q->has_range ? 1u : 0u;
-            vq.start = q->start; vq.end = q->end;
+            if (!ready || !d_small || !d_f) return ST_E_HIP;
             uint64_t err = 0;
             flag.resize(nrec);
-            if (vcfc_query_match(d_in, d_rec, nrec, vq, d_f, d_small, s) != hipSuccess ||
+            if (q->run(d_in, d_rec, nrec, d_f, d_small, s) != hipSuccess ||
                 hipMemcpyAsync(&err, d_small, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
                 hipMemcpyAsync(flag.data(), d_f, nrec, hipMemcpyDeviceToHost, s) != hipSuccess ||
                 hipStreamSynchronize(s) != hipSuccess)
@@ -149,12 +147,25 @@ inline int counts_section(const uint8_t *h_in, uint64_t n, uint64_t S, const Que
 }
 
 // A whole .vcfc: header, then counts_section.
-inline int counts_file(const uint8_t *in, uint64_t n, const Query *q, Buffers &B, hipStream_t s, Result &R,
+inline int counts_file(const uint8_t *in, uint64_t n, const vcfc_dec::MatchStep *match, Buffers &B, hipStream_t s, Result &R,
                        uint64_t *data_off, uint64_t *S, uint64_t rec_batch = 1ull << 22) {
     R = Result();
     const int st = counts_header(in, n, data_off, S);
     if (st) return st;
-    return counts_section(in + *data_off, n - *data_off, *S, q, B, s, R, rec_batch);
+    return counts_section(in + *data_off, n - *data_off, *S, match, B, s, R, rec_batch);
+}
+
+// counts_file with one region (q == nullptr: every record)
+inline int counts_file(const uint8_t *in, uint64_t n, const Query *q, Buffers &B, hipStream_t s, Result &R,
+                       uint64_t *data_off, uint64_t *S, uint64_t rec_batch = 1ull << 22) {
+    R = Result();
+    if (!q) return counts_file(in, n, static_cast<const vcfc_dec::MatchStep *>(nullptr), B, s, R, data_off, S, rec_batch);
+    VcfcQuery vq;
+    const vcfc_dec::MatchStep match = vcfc_dec::region_step(q->ref, q->ref_len, q->has_range, q->start, q->end, &vq);
+    const int st = counts_header(in, n, data_off, S);
+    if (st) return st;
+    if (q->ref_len > 0xFFFFFFFFull) return ST_E_FORMAT;
+    return counts_section(in + *data_off, n - *data_off, *S, &match, B, s, R, rec_batch);
 }
 
 inline void put_numbers(std::vector<uint8_t> &out, const uint64_t *v, int k) {

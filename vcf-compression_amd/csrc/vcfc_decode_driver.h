@@ -112,10 +112,12 @@ inline void hop(const uint8_t *in, uint64_t n, std::vector<uint64_t> &rec) {
 // leave at its end: *stop = 1 where it throws (lines before it sunk), 2 where
 // its parse ends off the record end, at *cont (its line sunk).  *stop = 0:
 // all records decoded.  line_end (optional): the end of every sunk line,
-// counted from the first byte this call sinks.
+// counted from the first byte this call sinks.  strict: the plan is exact
+// from the start and any error word of a record ends the lines before it
+// (*stop = 1).
 inline int decode_records(const uint8_t *d_in, uint64_t n, uint64_t S, const uint64_t *d_rec, const uint8_t *d_select,
                           uint64_t nrec, Buffers &B, hipStream_t s, const Sink &sink, uint64_t out_batch, int *stop,
-                          uint64_t *cont, std::vector<uint64_t> *line_end = nullptr) {
+                          uint64_t *cont, std::vector<uint64_t> *line_end = nullptr, bool strict = false) {
     *stop = 0;
     if (!nrec) return ST_OK;
     const VcfcDecodeLayout L = vcfc_decode_workspace_layout(nrec);
@@ -136,7 +138,7 @@ inline int decode_records(const uint8_t *d_in, uint64_t n, uint64_t S, const uin
     // a batch whose write finds a record the light plan got wrong is
     // re-planned exactly (lines already sunk keep their bytes: every line
     // before the first wrong record had the right size)
-    bool exact = false;
+    bool exact = strict;
     uint64_t n_lines = 0;
     std::vector<uint64_t> loff;
     auto plan = [&]() -> int {
@@ -148,7 +150,7 @@ inline int decode_records(const uint8_t *d_in, uint64_t n, uint64_t S, const uin
         *stop = 0;
         if (err != VCFCD_NO_ERROR) {
             const uint64_t k = err >> 8;
-            if ((err & 0xFF) == 2) {   // parse of record k ends off its end: keep its line, continue there
+            if ((err & 0xFF) == 2 && !strict) {   // parse of record k ends off its end: keep its line, continue there
                 n_lines = k + 1;
                 *stop = 2;
                 if (hipMemcpyAsync(cont, a.end + k, 8, hipMemcpyDeviceToHost, s) != hipSuccess) return ST_E_HIP;
@@ -240,6 +242,66 @@ inline int decode_section(const uint8_t *h_in, uint64_t n, uint64_t S, Buffers &
     return stream_tail(B, s, sink, [&](uint8_t *out, uint64_t *dst) { return vcfc_decode_stream(d_in, n, p_stream, S, ~0ull, out, dst, s); });
 }
 
+// The match step of a query: who fills the flags.  prepare uploads what the
+// match reads (false: ST_E_HIP); run enqueues the match of records
+// [d_rec[i], d_rec[i + 1]), i < nrec: d_flag[i], and *d_err = the minimum
+// over records of (i << 8 | code) as vcfc_query_match defines it.  The
+// drivers of the selected decode, the subset decode and the counts take it,
+// so one region and a region table share their bodies.
+struct MatchStep {
+    std::function<bool(Buffers &, hipStream_t)> prepare;
+    std::function<hipError_t(const uint8_t *d_in, const uint64_t *d_rec, uint64_t nrec, uint8_t *d_flag, uint64_t *d_err,
+                             hipStream_t s)> run;
+};
+
+// The one-region step (k_query_match); *q receives the device query, for
+// the caller that goes on with vcfc_query_stream.
+inline MatchStep region_step(const uint8_t *qref, uint64_t qref_len, int has_range, uint64_t qstart, uint64_t qend,
+                             VcfcQuery *q) {
+    q->ref = nullptr; q->ref_len = (uint32_t)qref_len; q->has_range = has_range ? 1u : 0u; q->start = qstart; q->end = qend;
+    MatchStep m;
+    m.prepare = [=](Buffers &B, hipStream_t s) { return (q->ref = upload(B, Buffers::QREF, qref, qref_len, s)) != nullptr; };
+    m.run = [=](const uint8_t *d_in, const uint64_t *d_rec, uint64_t nrec, uint8_t *d_flag, uint64_t *d_err, hipStream_t s) {
+        return vcfc_query_match(d_in, d_rec, nrec, *q, d_flag, d_err, s);
+    };
+    return m;
+}
+
+// What matched_records leaves for its caller.
+struct Matched {
+    std::vector<uint64_t> rec;   // the hopped record starts; back() = where hopping stopped
+    const uint8_t *d_in = nullptr;
+    uint64_t nrec = 0;
+    uint64_t err = VCFCD_NO_ERROR;   // the match's error word
+    uint64_t k = 0;              // records before the first match error
+    int stop = 0;                // decode_records' verdict over records [0, k)
+    uint64_t cont = 0;
+};
+
+// Steps 1 and 2 of a query over a data section: hop the LEN headers, fill the
+// flags with `match`, decode the flagged records before the first match
+// error through decode_records.
+inline int matched_records(const uint8_t *h_in, uint64_t n, uint64_t S, const MatchStep &match, Buffers &B, hipStream_t s,
+                           const Sink &sink, uint64_t out_batch, bool strict, Matched &M) {
+    hop(h_in, n, M.rec);
+    M.nrec = M.k = M.rec.size() - 1;
+    M.d_in = upload(B, Buffers::IN, h_in, n, s);
+    const bool ready = match.prepare(B, s);
+    uint64_t *d_small = static_cast<uint64_t *>(B.get(Buffers::SMALL, 64));
+    if (!M.d_in || !ready || !d_small) return ST_E_HIP;
+    if (!M.nrec) return ST_OK;
+    const uint64_t *d_rec = reinterpret_cast<const uint64_t *>(
+        upload(B, Buffers::REC, reinterpret_cast<const uint8_t *>(M.rec.data()), 8 * (M.nrec + 1), s));
+    uint8_t *d_flag = static_cast<uint8_t *>(B.get(Buffers::FLAG, M.nrec + 64));
+    if (!d_rec || !d_flag) return ST_E_HIP;
+    if (match.run(M.d_in, d_rec, M.nrec, d_flag, d_small, s) != hipSuccess ||
+        hipMemcpyAsync(&M.err, d_small, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+        return ST_E_HIP;
+    // records before the first irregular one k: the matching ones decode
+    if (M.err != VCFCD_NO_ERROR) M.k = M.err >> 8;
+    return decode_records(M.d_in, n, S, d_rec, d_flag, M.k, B, s, sink, out_batch, &M.stop, &M.cont, nullptr, strict);
+}
+
 // Range query over a .vcfc data section (query_compressed_file, reference
 // src/main.cpp:3777-3929): the matching lines, no header.
 //   1. hop the LEN headers; one lane per record finds CHROM/POS and the
@@ -253,40 +315,39 @@ inline int query_section(const uint8_t *h_in, uint64_t n, uint64_t S, const uint
                          int has_range, uint64_t qstart, uint64_t qend, Buffers &B, hipStream_t s, const Sink &sink,
                          uint64_t out_batch = 1ull << 30) {
     if (qref_len > 0xFFFFFFFFull) return ST_E_FORMAT;
-    std::vector<uint64_t> rec;
-    hop(h_in, n, rec);
-    const uint64_t nrec = rec.size() - 1;
-    const uint8_t *d_in = upload(B, Buffers::IN, h_in, n, s);
-    const uint8_t *d_ref = upload(B, Buffers::QREF, qref, qref_len, s);
-    uint64_t *d_small = static_cast<uint64_t *>(B.get(Buffers::SMALL, 64));
-    if (!d_in || !d_ref || !d_small) return ST_E_HIP;
     VcfcQuery q;
-    q.ref = d_ref; q.ref_len = (uint32_t)qref_len; q.has_range = has_range ? 1u : 0u; q.start = qstart; q.end = qend;
-    uint64_t p_stream = rec.back();
-    if (nrec) {
-        const uint64_t *d_rec = reinterpret_cast<const uint64_t *>(
-            upload(B, Buffers::REC, reinterpret_cast<const uint8_t *>(rec.data()), 8 * (nrec + 1), s));
-        uint8_t *d_flag = static_cast<uint8_t *>(B.get(Buffers::FLAG, nrec + 64));
-        if (!d_rec || !d_flag) return ST_E_HIP;
-        uint64_t err = 0;
-        if (vcfc_query_match(d_in, d_rec, nrec, q, d_flag, d_small, s) != hipSuccess ||
-            hipMemcpyAsync(&err, d_small, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-            return ST_E_HIP;
-        // records before the first irregular one k: the matching ones decode
-        const uint64_t k = err == VCFCD_NO_ERROR ? nrec : err >> 8;
-        int stop = 0;
-        uint64_t cont = 0;
-        int st = decode_records(d_in, n, S, d_rec, d_flag, k, B, s, sink, out_batch, &stop, &cont);
-        if (st) return st;
-        if (stop == 1) return ST_E_FORMAT;
-        if (stop == 2) p_stream = cont;
-        else if (k < nrec) {
-            if ((err & 0xFF) == 2) return ST_E_FORMAT;   // POS of record k does not parse
-            p_stream = rec[k];
+    const MatchStep match = region_step(qref, qref_len, has_range, qstart, qend, &q);
+    Matched M;
+    const int st = matched_records(h_in, n, S, match, B, s, sink, out_batch, false, M);
+    if (st) return st;
+    uint64_t p_stream = M.rec.back();
+    if (M.nrec) {
+        if (M.stop == 1) return ST_E_FORMAT;
+        if (M.stop == 2) p_stream = M.cont;
+        else if (M.k < M.nrec) {
+            if ((M.err & 0xFF) == 2) return ST_E_FORMAT;   // POS of record k does not parse
+            p_stream = M.rec[M.k];
         }
     }
     if (p_stream >= n) return ST_OK;
+    const uint8_t *d_in = M.d_in;
     return stream_tail(B, s, sink, [&](uint8_t *out, uint64_t *dst) { return vcfc_query_stream(d_in, n, p_stream, S, q, out, dst, s); });
+}
+
+// Region-list query over a .vcfc data section: the lines of
+// the records `match` flags, in file order.  ST_E_FORMAT at the first record
+// with a match error and at the first flagged record the exact decoder
+// reports in its error word, the flagged records' lines before it sunk; after
+// all lines, ST_E_FORMAT where the LEN hops stop with 8 or more bytes left.
+// There is no byte-serial continuation: the action has no reference
+// counterpart on a malformed file.
+inline int query_regions_section(const uint8_t *h_in, uint64_t n, uint64_t S, const MatchStep &match, Buffers &B,
+                                 hipStream_t s, const Sink &sink, uint64_t out_batch = 1ull << 30) {
+    Matched M;
+    const int st = matched_records(h_in, n, S, match, B, s, sink, out_batch, true, M);
+    if (st) return st;
+    if (M.stop || M.k < M.nrec) return ST_E_FORMAT;
+    return n - M.rec.back() >= 8 ? ST_E_FORMAT : ST_OK;   // fewer than 8 bytes left: a clean end
 }
 
 

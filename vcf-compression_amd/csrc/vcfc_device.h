@@ -340,6 +340,37 @@ hipError_t vcfc_query_stream(const uint8_t *in, uint64_t n, uint64_t p, uint64_t
                              uint64_t *st, hipStream_t s);
 
 // ---------------------------------------------------------------------------
+// Region-list match (vcfc_regions.hip).  The table is one
+// position-independent blob, built and validated on the host
+// (vcfc_regions_driver.h), little-endian, offsets from its first byte:
+//   VcfcRegionsHeader
+//   VcfcRegionName[n_names]   sorted by (len, bytes); the wildcard "" is first
+//   uint64 starts[n_intervals], uint64 ends[n_intervals]   (8-byte aligned)
+//   the names' bytes
+// A name's intervals [iv_first, iv_first + iv_count) are sorted by start and
+// disjoint, so the last start <= POS decides a record.
+#define VCFC_REGIONS_MAGIC 0x47524356u   // "VCRG"
+#define VCFC_REGIONS_VERSION 1u
+struct VcfcRegionsHeader {
+    uint32_t magic, version;
+    uint32_t n_names, n_intervals;
+    uint32_t off_names, off_starts, off_ends, off_bytes;
+    uint32_t total_bytes;   // the blob's size (< 4 GiB)
+    uint32_t n_bytes;       // bytes of all names
+    uint32_t pad[2];
+};
+struct VcfcRegionName {
+    uint32_t byte_off;      // from off_bytes
+    uint32_t len;
+    uint32_t iv_first, iv_count;
+};
+// one lane per record, as vcfc_query_match (same flags' meaning, same err
+// word): flag[i] = 1 if the record matches a region of the validated table
+// at `table` (device memory)
+hipError_t vcfc_regions_match(const uint8_t *in, const uint64_t *rec_start, uint64_t n, const uint8_t *table,
+                              uint8_t *flag, uint64_t *err, hipStream_t s);
+
+// ---------------------------------------------------------------------------
 // Line index of an input chunk (vcfc_ingest.hip; reference compress()'s
 // getline loop, src/compress.cpp:218-238).
 struct VcfcLineIndex {

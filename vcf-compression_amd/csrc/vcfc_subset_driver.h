@@ -10,8 +10,9 @@
 //   4. write the lines before it in output batches;
 //   5. VCFC_E_FORMAT at the first record that is not regular, or where
 //      hopping stopped with 8 or more bytes left.
-// The query variant runs the range query's match step first (its kernel and
-// error word unchanged) and decodes the matching records only.
+// The query variants run a match step first (vcfc_dec::MatchStep: the range
+// query's, kernel and error word unchanged, or a region table's, DESIGN.md
+// §4k) and decode the matching records only.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -151,29 +152,25 @@ inline int decode_section(const uint8_t *h_in, uint64_t n, uint64_t S, const std
     return n - rec.back() >= 8 ? ST_E_FORMAT : ST_OK;   // fewer than 8 bytes left: a clean end
 }
 
-// The matching records' lines (no header): matched exactly as
-// vcfc_dec::query_section matches them; only matching records must be
-// regular.  A match error at record k stops there.
-inline int query_section(const uint8_t *h_in, uint64_t n, uint64_t S, const std::vector<uint32_t> &csort,
-                         const std::vector<uint32_t> &rank, const uint8_t *qref, uint64_t qref_len, int has_range,
-                         uint64_t qstart, uint64_t qend, Buffers &B, hipStream_t s, const Sink &sink,
-                         uint64_t out_batch = 1ull << 30) {
-    if (qref_len > 0xFFFFFFFFull) return ST_E_FORMAT;
+// The lines (no header) of the records `match` flags (vcfc_dec::MatchStep: one
+// region, or a region table); only flagged records must be regular.  A match
+// error at record k stops there.
+inline int matched_section(const uint8_t *h_in, uint64_t n, uint64_t S, const std::vector<uint32_t> &csort,
+                           const std::vector<uint32_t> &rank, const vcfc_dec::MatchStep &match, Buffers &B, hipStream_t s,
+                           const Sink &sink, uint64_t out_batch = 1ull << 30) {
     std::vector<uint64_t> rec;
     vcfc_dec::hop(h_in, n, rec);
     const uint64_t nrec = rec.size() - 1;
     if (nrec) {
         const uint8_t *d_in = vcfc_dec::upload(B, Buffers::IN, h_in, n, s);
-        const uint8_t *d_ref = vcfc_dec::upload(B, Buffers::QREF, qref, qref_len, s);
+        const bool ready = match.prepare(B, s);
         uint64_t *d_small = static_cast<uint64_t *>(B.get(Buffers::SMALL, 64));
         const uint64_t *d_rec = reinterpret_cast<const uint64_t *>(
             vcfc_dec::upload(B, Buffers::REC, reinterpret_cast<const uint8_t *>(rec.data()), 8 * rec.size(), s));
         uint8_t *d_flag = static_cast<uint8_t *>(B.get(Buffers::FLAG, nrec + 64));
-        if (!d_in || !d_ref || !d_small || !d_rec || !d_flag) return ST_E_HIP;
-        VcfcQuery q;
-        q.ref = d_ref; q.ref_len = (uint32_t)qref_len; q.has_range = has_range ? 1u : 0u; q.start = qstart; q.end = qend;
+        if (!d_in || !ready || !d_small || !d_rec || !d_flag) return ST_E_HIP;
         uint64_t err = 0;
-        if (vcfc_query_match(d_in, d_rec, nrec, q, d_flag, d_small, s) != hipSuccess ||
+        if (match.run(d_in, d_rec, nrec, d_flag, d_small, s) != hipSuccess ||
             hipMemcpyAsync(&err, d_small, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
             return ST_E_HIP;
         const uint64_t k = err == VCFCD_NO_ERROR ? nrec : err >> 8;   // the first record with a match error
@@ -183,6 +180,18 @@ inline int query_section(const uint8_t *h_in, uint64_t n, uint64_t S, const std:
         if (stop || k < nrec) return ST_E_FORMAT;
     }
     return n - rec.back() >= 8 ? ST_E_FORMAT : ST_OK;
+}
+
+// matched_section with one region: matched exactly as vcfc_dec::query_section
+// matches.
+inline int query_section(const uint8_t *h_in, uint64_t n, uint64_t S, const std::vector<uint32_t> &csort,
+                         const std::vector<uint32_t> &rank, const uint8_t *qref, uint64_t qref_len, int has_range,
+                         uint64_t qstart, uint64_t qend, Buffers &B, hipStream_t s, const Sink &sink,
+                         uint64_t out_batch = 1ull << 30) {
+    if (qref_len > 0xFFFFFFFFull) return ST_E_FORMAT;
+    VcfcQuery q;
+    return matched_section(h_in, n, S, csort, rank, vcfc_dec::region_step(qref, qref_len, has_range, qstart, qend, &q), B, s,
+                           sink, out_batch);
 }
 
 // Resolve a comma-separated name list against the '#CHROM' line (the first

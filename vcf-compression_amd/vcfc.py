@@ -55,6 +55,10 @@ EXPORTS = [
     "vcfc_query_samples_buffer", "vcfc_query_samples_file",
     "vcfc_counts_workspace_size", "vcfc_counts_lds_samples", "vcfc_genotype_counts_device",
     "vcfc_genotype_counts_buffer", "vcfc_genotype_counts_file",
+    "vcfc_regions_build", "vcfc_regions_workspace_size", "vcfc_regions_upload", "vcfc_regions_match_device",
+    "vcfc_query_regions_buffer", "vcfc_query_regions_file",
+    "vcfc_query_samples_regions_buffer", "vcfc_query_samples_regions_file",
+    "vcfc_genotype_counts_regions_buffer", "vcfc_genotype_counts_regions_file",
 ]
 LINE_INDEX_HOP, LINE_INDEX_SCAN = 0, 1                       # include/vcfc.h VCFC_LINE_INDEX_*
 TRACE_INGEST, TRACE_DEVICE, TRACE_SPARSE_QUERY = 1, 2, 4     # include/vcfc.h VCFC_TRACE_*
@@ -134,13 +138,26 @@ def lib():
                                             vp, u64, ctypes.POINTER(u64), vp, u64, ctypes.POINTER(u64),
                                             ctypes.POINTER(u64)],
             "vcfc_genotype_counts_file": [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int,
-                                          ctypes.c_char_p, u64, ctypes.c_int, u64, u64]}
+                                          ctypes.c_char_p, u64, ctypes.c_int, u64, u64],
+            # region lists
+            "vcfc_regions_build": [ctypes.c_char_p, u64, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(u64),
+                                   ctypes.POINTER(u64)],
+            "vcfc_regions_workspace_size": [u64],
+            "vcfc_regions_upload": [vp, u64, vp, u64, vp],
+            "vcfc_regions_match_device": [vp, vp, u64, vp, u64, vp, vp, vp],
+            "vcfc_query_regions_buffer": [vp, vp, u64, vp, u64, vp, u64, ctypes.POINTER(u64)],
+            "vcfc_query_regions_file": [vp, ctypes.c_char_p, vp, u64, ctypes.c_int],
+            "vcfc_query_samples_regions_buffer": [vp, vp, u64, vp, u64, vp, u64, vp, u64, ctypes.POINTER(u64)],
+            "vcfc_query_samples_regions_file": [vp, ctypes.c_char_p, vp, u64, vp, u64, ctypes.c_int],
+            "vcfc_genotype_counts_regions_buffer": [vp, vp, u64, vp, u64, vp, vp, u64, ctypes.POINTER(u64), vp, u64,
+                                                    ctypes.POINTER(u64), ctypes.POINTER(u64)],
+            "vcfc_genotype_counts_regions_file": [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, vp, u64]}
     for name, args in late.items():
         if hasattr(L, name):
             getattr(L, name).argtypes = args
     for name in ("vcfc_index_workspace_size", "vcfc_sparse_index_workspace_size", "vcfc_sparse_index_offset",
                  "vcfc_decode_sizes_workspace_size", "vcfc_subset_workspace_size", "vcfc_counts_workspace_size",
-                 "vcfc_counts_lds_samples"):
+                 "vcfc_counts_lds_samples", "vcfc_regions_workspace_size"):
         if hasattr(L, name):
             getattr(L, name).restype = u64
     L.vcfc_record_hash_device.argtypes = [vp, vp, u64, vp, vp]
@@ -577,6 +594,78 @@ class Context:
             len(ref), int(query.has_range) if query is not None else 0, query.start if query is not None else 0,
             query.end if query is not None else 0))
 
+    def query_regions_buffer(self, data, regions, cap=None):
+        """query-regions: the lines (no header) of the records
+        matching at least one region, in file order, each once.  `regions` is
+        region text (BED or <ref>[:<start>-<end>] lines) or a table from
+        regions_build.  Returns (status, bytes): on VCFC_E_FORMAT the bytes
+        are the matching records' lines before the record it stopped at."""
+        tab = np.frombuffer(_regions_table(regions), dtype=np.uint8)
+        src = np.frombuffer(data, dtype=np.uint8)
+        cap = cap if cap is not None else 16 * len(data) + 4096
+        while True:
+            out = np.empty(max(cap, 1), dtype=np.uint8)
+            n = ctypes.c_uint64(0)
+            st = _need("vcfc_query_regions_buffer")(self._h, src.ctypes.data, len(data), tab.ctypes.data, len(tab),
+                                                    out.ctypes.data, cap, ctypes.byref(n))
+            if st == E_NOSPACE and n.value > cap:
+                cap = n.value
+                continue
+            return st, out[:n.value].tobytes()
+
+    def query_regions_file(self, in_path, regions, out_fd=1):
+        """As `main query-regions <file> <regions-file>`, with region text or a table."""
+        tab = np.frombuffer(_regions_table(regions), dtype=np.uint8)
+        raise_for(_need("vcfc_query_regions_file")(self._h, in_path.encode(), tab.ctypes.data, len(tab), out_fd))
+
+    def query_samples_regions_buffer(self, data, regions, cols, cap=None):
+        """query_samples_buffer over a region list.  Returns (status, bytes)."""
+        tab = np.frombuffer(_regions_table(regions), dtype=np.uint8)
+        src = np.frombuffer(data, dtype=np.uint8)
+        c = np.asarray(cols, dtype=np.uint32)
+        cap = cap if cap is not None else len(data) + 16 * len(c) * (len(data) // 64 + 1) + 4096
+        while True:
+            out = np.empty(max(cap, 1), dtype=np.uint8)
+            n = ctypes.c_uint64(0)
+            st = _need("vcfc_query_samples_regions_buffer")(self._h, src.ctypes.data, len(data), tab.ctypes.data,
+                                                            len(tab), c.ctypes.data, len(c), out.ctypes.data, cap,
+                                                            ctypes.byref(n))
+            if st == E_NOSPACE and n.value > cap:
+                cap = n.value
+                continue
+            return st, out[:n.value].tobytes()
+
+    def query_samples_regions_file(self, in_path, regions, cols, out_fd=1):
+        tab = np.frombuffer(_regions_table(regions), dtype=np.uint8)
+        c = np.asarray(cols, dtype=np.uint32)
+        raise_for(_need("vcfc_query_samples_regions_file")(self._h, in_path.encode(), tab.ctypes.data, len(tab),
+                                                           c.ctypes.data, len(c), out_fd))
+
+    def genotype_counts_regions_buffer(self, data, regions):
+        """genotype_counts_buffer over a region list: (status, record_indices,
+        rows, samples), `last_counts_record` as there."""
+        tab = np.frombuffer(_regions_table(regions), dtype=np.uint8)
+        src = np.frombuffer(data, dtype=np.uint8)
+        cap, scap = len(data) // 12 + 16, 4096
+        while True:
+            idx, rows = np.zeros(cap, dtype=np.uint64), np.zeros((cap, 8), dtype=np.uint32)
+            st_tab = np.zeros((scap, 5), dtype=np.uint64)
+            n, ns, bad = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+            st = _need("vcfc_genotype_counts_regions_buffer")(
+                self._h, src.ctypes.data, len(data), tab.ctypes.data, len(tab), idx.ctypes.data, rows.ctypes.data, cap,
+                ctypes.byref(n), st_tab.ctypes.data, scap, ctypes.byref(ns), ctypes.byref(bad))
+            if st == E_NOSPACE and (n.value > cap or ns.value > scap):
+                cap, scap = max(cap, n.value), max(scap, ns.value)
+                continue
+            self.last_counts_record = bad.value
+            return st, idx[:n.value].copy(), rows[:n.value].copy(), st_tab[:ns.value].copy() if st == OK else None
+
+    def genotype_counts_regions_file(self, in_path, variants_path, samples_path, regions):
+        """As `main genotype-counts-regions <in.vcfc> <variants.tsv> <samples.tsv> <regions-file>`."""
+        tab = np.frombuffer(_regions_table(regions), dtype=np.uint8)
+        raise_for(_need("vcfc_genotype_counts_regions_file")(self._h, in_path.encode(), variants_path.encode(),
+                                                             samples_path.encode(), tab.ctypes.data, len(tab)))
+
     def sparse_query_status(self, in_path, query):
         """query_sparse_file_fd (reference src/main.cpp:235-582) over a sparse
         file: (status, stdout bytes); E_FORMAT where the reference throws (the
@@ -819,6 +908,52 @@ def query_match_device(d_in, d_rec_start, n, d_ref, ref_len, has_range, start, e
     """Device match step of the range query (see include/vcfc.h)."""
     return lib().vcfc_query_match_device(d_in, d_rec_start, n, d_ref, ref_len, int(has_range), start, end, d_flag,
                                          d_err, stream)
+
+
+REGIONS_MAGIC = b"VCRG"   # the first bytes of a region table (csrc/vcfc_device.h VCFC_REGIONS_MAGIC)
+
+
+def regions_build(text):
+    """The region table (bytes) of region text, one region per line: BED
+    (name TAB start TAB end, 0-based half-open) or <ref>[:<start>-<end>]
+    (include/vcfc.h vcfc_regions_build).  Raises ValueError naming the
+    1-based line that does not parse."""
+    text = text.encode() if isinstance(text, str) else bytes(text)
+    nb, nr, bad = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    f = _need("vcfc_regions_build")
+    st = f(text, len(text), None, 0, ctypes.byref(nb), ctypes.byref(nr), ctypes.byref(bad))
+    out = np.zeros(max(nb.value, 1), dtype=np.uint8)
+    if st == E_NOSPACE:
+        st = f(text, len(text), out.ctypes.data, nb.value, ctypes.byref(nb), ctypes.byref(nr), ctypes.byref(bad))
+    if st == E_ARG and bad.value:
+        line = text.split(b"\n")[bad.value - 1].rstrip(b"\r")
+        raise ValueError("Failed to parse region at line %d: %s" % (bad.value, line.decode(errors="replace")))
+    raise_for(st)
+    return out[:nb.value].tobytes()
+
+
+def _regions_table(regions):
+    """A table as it is; region text built."""
+    if isinstance(regions, (bytes, bytearray)) and bytes(regions[:4]) == REGIONS_MAGIC:
+        return bytes(regions)
+    return regions_build(regions)
+
+
+def regions_workspace_size(table_bytes):
+    return int(_need("vcfc_regions_workspace_size")(table_bytes))
+
+
+def regions_upload(table, d_ws, ws_bytes, stream=0):
+    """Validate a table from regions_build and copy it into the device
+    workspace d_ws (include/vcfc.h vcfc_regions_upload).  Returns the status."""
+    t = np.frombuffer(table, dtype=np.uint8)
+    return _need("vcfc_regions_upload")(t.ctypes.data if len(t) else None, len(t), d_ws, ws_bytes, stream)
+
+
+def regions_match_device(d_in, d_rec_start, n, d_ws, ws_bytes, d_flag, d_err, stream=0):
+    """query_match_device with the table uploaded into d_ws in place of one
+    region.  Returns the status; enqueued on `stream`."""
+    return _need("vcfc_regions_match_device")(d_in, d_rec_start, n, d_ws, ws_bytes, d_flag, d_err, stream)
 
 
 def synth_rows_device(d_buf, d_line_off, n, d_prefix, d_prefix_off, d_row_af, samples, law, seed, stream=0,
