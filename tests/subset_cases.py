@@ -210,29 +210,7 @@ def column_sets(S, seed=0):
     return out
 
 
-def rec(req, samples_bytes, lf=b"\n", reqlen=None, flags=(0xC0, 0xC0)):
-    """A record; reqlen / flags: a REQ length field other than len(req), the
-    two header bytes' top bits other than 11 (LEN stays right either way)."""
-    body = req + samples_bytes + lf
-    L = len(body) + 4
-    n = len(req) if reqlen is None else reqlen
-    return bytes([flags[0] | (L >> 24) & 0x3F, (L >> 16) & 0xFF, (L >> 8) & 0xFF, L & 0xFF, flags[1] | (n >> 24) & 0x3F,
-                  (n >> 16) & 0xFF, (n >> 8) & 0xFF, n & 0xFF]) + body
-
-
-def req_of(i):
-    return b"22\t%d\trs%d\tA\tG\t50\tPASS\tAC=%d\tGT\t" % (100 + i, i, i)
-
-
-def fill(n, code=0x00):
-    """n tokens of one class as run bytes (0|0: up to 127 a byte, else 31)."""
-    m = 127 if code == 0 else 31
-    out = b""
-    while n:
-        k = min(n, m)
-        out += bytes([code | k])
-        n -= k
-    return out
+rec, req_of, fill = D.rec, D.req_of, D.fill   # (the record builders: decode_cases.py)
 
 
 HS = 600   # samples of the hand-built records

@@ -44,3 +44,18 @@ def test_valid_files_match_oracle(seed):
 def test_mutated_files_match_oracle(seed):
     for name, data in D.mutated_files(seed):
         check(data, name)
+
+
+@pytest.mark.parametrize("out_batch", [1 << 12, 1 << 30])
+def test_edge_files_match_oracle(out_batch):
+    """decode_cases.edge_files(): the writer's REQ copy, tiles, windows and
+    staged pieces at their edges.  At 1 << 12 a batch holds a line or two, so
+    the batch loop of decode_records runs many times and late_bad's wrong
+    light plan is found with lines already sunk; at 1 << 30 every file is one
+    batch."""
+    exp = D.edge_expected()
+    for name, data, status in D.edge_files():
+        st_o, want, _ = exp[name]
+        st, got = E.emu_decompress(data, out_batch=out_batch, cap=D.edge_cap(data))
+        assert st == status, (name, st, st_o)
+        assert got == want, (name, len(got), len(want))

@@ -65,6 +65,20 @@ def test_mutated_files_match_oracle(ctx, seed):
         check(ctx, data, name)
 
 
+def test_edge_files_match_oracle(ctx):
+    """decode_cases.edge_files(): the writer's REQ copy, tiles, windows and
+    staged pieces at their edges.  The C ABI has one output batch size, so
+    each file is one batch here; the batch loop at small batches (late_bad's
+    re-plan with lines already written) stays an emulator test
+    (test_decode_emu.py)."""
+    exp = D.edge_expected()
+    for name, data, status in D.edge_files():
+        st_o, want, _ = exp[name]
+        st, got = ctx.decompress_buffer(data, cap=D.edge_cap(data))
+        assert st == status, (name, st, st_o)
+        assert got == want, (name, len(got), len(want))
+
+
 def test_round_trip_2504x4000(ctx):
     import random_vcf
     buf = io.BytesIO()

@@ -80,6 +80,17 @@ def test_mutated_decode_files_match_oracle(ctx, seed):
             check(ctx, data, q, name)
 
 
+def test_edge_files_match_oracle(ctx):
+    """decode_cases.edge_files() through the selected kernels (one output
+    batch a query: the batch loop is an emulator test, test_query_emu.py)."""
+    exp = D.edge_expected()
+    for name, data, _ in D.edge_files():
+        for q, (st_o, want) in exp[name][2].items():
+            st, got = ctx.query_buffer(data, q, cap=D.edge_cap(data))
+            assert st == (OK if st_o == 0 else E_FORMAT), (name, q, st, st_o)
+            assert got == want, (name, q, len(got), len(want))
+
+
 def test_query_2504x4000(ctx):
     import random_vcf
     buf = io.BytesIO()

@@ -13,6 +13,7 @@ import tempfile
 import numpy as np
 import pytest
 
+import decode_cases as D
 import golden_io as G
 import regions_cases as RC
 import subset_cases as SC
@@ -223,6 +224,25 @@ def test_driver_arguments(ctx, qry, qsam, cnt):
     want = RC.query_regions(data, RC.parse_text(RC.SETS["A"]))
     assert len(want[1]) > 0 and ctx.query_regions_buffer(data, table, cap=5) == want
     assert ctx.query_samples_regions_buffer(data, table, [1], cap=5) == RC.query_samples_regions(data, RC.parse_text(RC.SETS["A"]), [1])
+
+
+def test_decoder_edge_files(ctx):
+    """decode_cases.edge_files() through query-regions, the strict path (every
+    matching record planned exactly): each of the range queries' intervals as
+    a one-region list, held to the oracle's range query, and four of them as
+    one list, held to the restatement.  One output batch a call: the batch
+    loop is an emulator test."""
+    exp = D.edge_expected()
+    both = b"22:103-110\n:0-101\n22:109-109\n21\n"
+    for name, data, _ in D.edge_files():
+        cap = D.edge_cap(data)
+        for q, (st_o, want) in exp[name][2].items():
+            got = ctx.query_regions_buffer(data, build(q + b"\n"), cap=cap)
+            assert got[0] == (OK if st_o == 0 else E_FORMAT) and got[1] == want, (name, q, got[0], st_o, len(got[1]), len(want))
+        want = RC.query_regions(data, RC.parse_text(both))
+        got = ctx.query_regions_buffer(data, build(both), cap=cap)
+        assert got == want, (name, got[0], want[0], len(got[1]), len(want[1]))
+        assert 0 < want[1].count(b"\n") < D.records_in(data), name   # a non-empty proper subset of the records
 
 
 def test_reference_cli_golden(qry):

@@ -53,3 +53,14 @@ def test_mutated_decode_files_match_oracle():
     for name, data in D.mutated_files(5):
         for q in (b"22", b"22:110-120"):
             check(data, q, name)
+
+
+def test_edge_files_match_oracle():
+    """decode_cases.edge_files() through the selected kernels (k_dec_plan /
+    k_dec_write with a select flag per record)."""
+    exp = D.edge_expected()
+    for name, data, _ in D.edge_files():
+        for q, (st_o, want) in exp[name][2].items():
+            st, got = E.emu_query(data, *G.oracle_parse_query(q), out_batch=1 << 12, cap=D.edge_cap(data))
+            assert st == (OK if st_o == 0 else E_FORMAT), (name, q, st, st_o)
+            assert got == want, (name, q, len(got), len(want))
