@@ -88,9 +88,10 @@ def last_mispredict():
     return int(lib().emu_last_mispredict())
 
 
-def emu_encode(buf, line_off, line_len, cap=None):
+def emu_encode(buf, line_off, line_len, cap=None, total=None):
     """Run the product encode pipeline on the emulator (output capacity
-    `cap`, default the bound).  Returns (status, records bytes, rec_off
+    `cap`, default the bound; `total`: a total_line_bytes above the lines'
+    sum, EMU_TOTAL_BYTES).  Returns (status, records bytes, rec_off
     array, err_word); the number of rows the fast kernel handed to the
     general kernel is left in LAST_RETRIES[0]."""
     n = len(line_off)
@@ -104,8 +105,14 @@ def emu_encode(buf, line_off, line_len, cap=None):
     err = ctypes.c_uint64(0)
     sw = ctypes.c_uint64(0)
     rt = ctypes.c_uint32(0)
-    st = lib().emu_encode_rows(src.ctypes.data, lo.ctypes.data, ll.ctypes.data, n, out.ctypes.data, cap,
-                               rec_off.ctypes.data, ctypes.byref(err), ctypes.byref(sw), ctypes.byref(rt))
+    if total is not None:
+        os.environ["EMU_TOTAL_BYTES"] = "%d" % total
+    try:
+        st = lib().emu_encode_rows(src.ctypes.data, lo.ctypes.data, ll.ctypes.data, n, out.ctypes.data, cap,
+                                   rec_off.ctypes.data, ctypes.byref(err), ctypes.byref(sw), ctypes.byref(rt))
+    finally:
+        if total is not None:
+            del os.environ["EMU_TOTAL_BYTES"]
     LAST_RETRIES[0] = rt.value
     total = int(rec_off[n]) if n else 0
     if cap < full:

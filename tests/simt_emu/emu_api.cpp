@@ -38,6 +38,9 @@ extern "C" int emu_encode_rows(const uint8_t *buf, const uint64_t *line_off, con
                                uint64_t *err_word, uint64_t *switches, uint32_t *retries) {
     uint64_t total = 0;
     for (uint64_t i = 0; i < n; i++) total += line_len[i];
+    // (tests: a larger total_line_bytes, as the ABI allows: the workspace layout, the
+    // primary staging size and the compaction grid follow it)
+    if (const char *t = getenv("EMU_TOTAL_BYTES")) total = std::max<uint64_t>(total, strtoull(t, nullptr, 10));
     VcfcWorkspaceLayout L = vcfc_encode_workspace_layout(n, total);
     uint8_t *ws = (uint8_t *)aligned_alloc(256, (L.total + 255) & ~255ull);
     memset(ws, 0xCD, L.total);  // poison: stale workspace must not leak into results

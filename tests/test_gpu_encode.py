@@ -1,5 +1,12 @@
 """GPU parity: the HIP path (through the C ABI) against the reference's golden
-vectors and the oracle.  Needs a gfx950 GPU (-m gpu)."""
+vectors and the oracle.  Needs a gfx950 GPU (-m gpu).
+
+Shared with the emulator tests (test_kernel_emu.py): the rows of
+encode_cases.py -- every seeded and hand-built family, at every alignment of
+the buffer here, the out_cap values of cap_values() and the error batches.
+The emulator tests show which kernel path each family takes (the path is a
+function of the row's bytes); these run the lanes at once, which the
+emulator's fibers do not."""
 import hashlib
 import io
 import os
@@ -10,6 +17,7 @@ import tempfile
 import numpy as np
 import pytest
 
+import encode_cases as C
 import golden_io as G
 
 pytestmark = pytest.mark.gpu
@@ -218,11 +226,10 @@ def test_variable_token_rows(ctx, seed):
     fields, a trailing TAB, CR, a failure in the third chunk), through
     compress_buffer: byte-exact against the oracle."""
     import random
-    import test_kernel_emu as T
     rnd = random.Random(seed)
-    lines = T._var_rows(rnd, 120, ["hap", "dot", "long", "ones", "runs", "gdg"])
-    lines += [T.PFX_V + b"0\t1|1\t10\t0|0", T.PFX_V + b"0\t\t1|1\t0", T.PFX_V + b"1\t0|0\t",
-              T.PFX_V + b"\t".join([b"0"] * 2000 + [b"10", b"11", b"1"])]
+    lines = C.var_rows(rnd, 120, ["hap", "dot", "long", "ones", "runs", "gdg"])
+    lines += [C.PFX_V + b"0\t1|1\t10\t0|0", C.PFX_V + b"0\t\t1|1\t0", C.PFX_V + b"1\t0|0\t",
+              C.PFX_V + b"\t".join([b"0"] * 2000 + [b"10", b"11", b"1"])]
     rnd.shuffle(lines)
     hdr = b"##fileformat=VCFv4.2\n#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tS0\n"
     data = hdr + b"\n".join(lines) + b"\n"
@@ -244,19 +251,18 @@ def test_predicted_deferred_records(ctx, odd):
     compaction and deferred pass lay the batch out again: byte-exact
     against the oracle through compress_buffer either way."""
     import random
-    import test_kernel_emu as T
     rnd = random.Random(hash(odd) & 0xFFFF)
-    lines = [T._gdg(rnd, 700) for _ in range(300)]
+    lines = [C.gdg(rnd, 700) for _ in range(300)]
     for i in range(17, 300, 61):
         if odd == "ntok":
-            lines[i] = T._gdg(rnd, 701)
+            lines[i] = C.gdg(rnd, 701)
         elif odd == "mixed_later":
-            lines[i] = T.PFX_V + b"\t".join([rnd.choice([b"0", b"1", b"."]) for _ in range(1100)] +
+            lines[i] = C.PFX_V + b"\t".join([rnd.choice([b"0", b"1", b"."]) for _ in range(1100)] +
                                             [rnd.choice([b"0|0", b"0|1"]) for _ in range(400)])
         elif odd == "general_later":
-            lines[i] = T.PFX_V + b"\t".join([b"0|1:33:99"] * 300 + [b"0|1:3:99"] * 2 + [b"0|1:33:99"] * 398)
+            lines[i] = C.PFX_V + b"\t".join([b"0|1:33:99"] * 300 + [b"0|1:3:99"] * 2 + [b"0|1:33:99"] * 398)
         elif odd == "long_then_plain":
-            lines[i] = T.PFX_V + b"\t".join([b"0|1:33:99"] + [rnd.choice([b"0|0", b"0|1"]) for _ in range(699)])
+            lines[i] = C.PFX_V + b"\t".join([b"0|1:33:99"] + [rnd.choice([b"0|0", b"0|1"]) for _ in range(699)])
     hdr = (b"##fileformat=VCFv4.2\n#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" +
            b"\t".join(b"S%d" % j for j in range(700)) + b"\n")
     data = hdr + b"\n".join(lines) + b"\n"
@@ -272,22 +278,21 @@ def test_unphased_rows_handed_on(ctx):
     more, single-chunk rows and rows starting with a plain token among them:
     byte-exact against the oracle through compress_buffer."""
     import random
-    import test_kernel_emu as T
     rnd = random.Random(5150)
     unph = [b"0/0", b"0/1", b"1/1", b"./."]
     S = 900
-    lines = [T.PFX_V + b"\t".join(rnd.choice(unph) for _ in range(S)) for _ in range(400)]
+    lines = [C.PFX_V + b"\t".join(rnd.choice(unph) for _ in range(S)) for _ in range(400)]
     for i in range(13, 400, 47):
         k = rnd.randrange(4)
         if k == 0:
-            lines[i] = T.PFX_V + b"\t".join([rnd.choice(unph) for _ in range(600)] +
+            lines[i] = C.PFX_V + b"\t".join([rnd.choice(unph) for _ in range(600)] +
                                             [rnd.choice([b"0|0", b"0|1"]) for _ in range(S - 600)])
         elif k == 1:
-            lines[i] = T.PFX_V + b"\t".join(rnd.choice(unph) for _ in range(S + 1))
+            lines[i] = C.PFX_V + b"\t".join(rnd.choice(unph) for _ in range(S + 1))
         elif k == 2:
-            lines[i] = T.PFX_V + b"\t".join(rnd.choice(unph) for _ in range(200))
+            lines[i] = C.PFX_V + b"\t".join(rnd.choice(unph) for _ in range(200))
         else:
-            lines[i] = T.PFX_V + b"\t".join([b"0|1"] + [rnd.choice(unph) for _ in range(S - 1)])
+            lines[i] = C.PFX_V + b"\t".join([b"0|1"] + [rnd.choice(unph) for _ in range(S - 1)])
     hdr = (b"##fileformat=VCFv4.2\n#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" +
            b"\t".join(b"S%d" % j for j in range(S)) + b"\n")
     data = hdr + b"\n".join(lines) + b"\n"
@@ -339,10 +344,9 @@ def test_mispredicted_batch_replayed_in_hip_graph(torch, vcfc):
     lays the batch out again through the gated launches -- records equal to
     the oracle's on each replay."""
     import random
-    import test_kernel_emu as T
     rnd = random.Random(77)
-    lines = [T._gdg(rnd, 700) for _ in range(200)]
-    lines[150] = T._gdg(rnd, 701)
+    lines = [C.gdg(rnd, 700) for _ in range(200)]
+    lines[150] = C.gdg(rnd, 701)
     buf = b"".join(ln + b"\n" for ln in lines)
     off = np.cumsum([0] + [len(ln) + 1 for ln in lines[:-1]]).astype(np.int64)
     ln_ = np.array([len(ln) for ln in lines], dtype=np.int32)
@@ -456,3 +460,122 @@ def test_line_longer_than_the_length_header_is_refused(torch, vcfc):
     r = rec.cpu().numpy()
     host = out[:int(r[2])].cpu().numpy().tobytes()
     assert host == G.oracle_encode_line(lines[0])[1] + G.oracle_encode_line(lines[1])[1]
+
+
+# ---- the rows of encode_cases.py, as test_kernel_emu.run places them ---------
+
+STRIDED_TOTAL = 24 << 20   # total_line_bytes from which k_compact_out strides a 2 048-block grid over the tiles
+
+
+def _device_encode_lines(torch, vcfc, lines, lead, cap=None, total=None):
+    """b"#" * lead, then the lines, each followed by LF, through
+    vcfc.encode_rows_device (out_cap `cap`, default the bound; total_line_bytes
+    `total`, default the lines' sum).  out holds cap + 4096 bytes, 0xEE before
+    the call.  Returns (out, rec_off, error word)."""
+    buf = bytearray(b"#" * lead)
+    offs, lens = [], []
+    for ln in lines:
+        offs.append(len(buf))
+        lens.append(len(ln))
+        buf += ln + b"\n"
+    dev = torch.device("cuda:0")
+    d_buf = torch.from_numpy(np.frombuffer(bytes(buf) + b"\0" * 64, dtype=np.uint8).copy()).to(dev)
+    d_off = torch.tensor(offs, dtype=torch.int64, device=dev)
+    d_len = torch.tensor(lens, dtype=torch.int32, device=dev)
+    n = len(lines)
+    total = sum(lens) if total is None else total
+    assert total >= sum(lens)
+    ws_bytes = vcfc.workspace_size(n, total)
+    cap = vcfc.encode_bound(n, total) if cap is None else cap
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    out = torch.full((cap + 4096,), 0xEE, dtype=torch.uint8, device=dev)
+    rec = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    err = torch.empty(1, dtype=torch.int64, device=dev)
+    vcfc.encode_rows_device(d_buf.data_ptr(), d_off.data_ptr(), d_len.data_ptr(), n, total, out.data_ptr(), cap,
+                            rec.data_ptr(), ws.data_ptr(), ws_bytes, err.data_ptr(),
+                            torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    return out, rec.cpu().numpy().astype(np.uint64), int(err.cpu().numpy().view(np.uint64)[0])
+
+
+def _check_records(vcfc, got, want, tag):
+    """err, every record and every offset against the oracle's records."""
+    out, rec, err = got
+    assert err == vcfc.NO_ERROR, (tag, hex(err))
+    assert np.array_equal(rec, np.cumsum([0] + [len(w) for w in want]).astype(np.uint64)), tag
+    host = out[:int(rec[-1])].cpu().numpy().tobytes()
+    if host != b"".join(want):
+        o = 0
+        for i, w in enumerate(want):
+            assert host[o:o + len(w)] == w, (tag, i)
+            o += len(w)
+
+
+@pytest.mark.parametrize("name,seed", C.all_families(), ids=lambda v: "%s" % (v,))
+def test_families_at_every_alignment(torch, vcfc, name, seed):
+    """Every family of encode_cases (the seeded ones and edge_rows()) with the
+    buffer starting 0 .. 15 bytes off a 16-byte boundary: no error, every
+    record and every offset equal to the oracle's."""
+    lines, want = C.family(name, seed), C.expected(name, seed)
+    for lead in range(16):
+        _check_records(vcfc, _device_encode_lines(torch, vcfc, lines, lead), want, (name, seed, lead))
+
+
+@pytest.mark.parametrize("base,pb", C.SIZE_BATCHES)
+def test_size_edge_both_primary_sizes(torch, vcfc, base, pb):
+    """The size_edge batches with prim_bytes 1024 and 2048 (a larger
+    total_line_bytes, or short rows behind the batch)."""
+    name = "size_edge_%d/%d" % (base, pb)
+    lines, total = C.size_edge_batch(base, pb)
+    assert C.prim_bytes(len(lines), sum(len(x) for x in lines) if total is None else total) == pb
+    want = [G.oracle_encode_line(x)[1] for x in lines]
+    for lead in (0, 1, 7, 15):
+        _check_records(vcfc, _device_encode_lines(torch, vcfc, lines, lead, total=total), want, (name, lead))
+
+
+def test_strided_compaction_grid(torch, vcfc):
+    """A total_line_bytes that gives k_compact_out its strided grid (8 192
+    tiles or more by the bound: 2 048 blocks, each over many tiles) on small
+    batches: the golden edge cases and the size_edge rows."""
+    good = [c for c in G.edge_cases()["cases"] if "record" in c]
+    batches = [("golden", [bytes.fromhex(c["line"]) for c in good], [bytes.fromhex(c["record"]) for c in good])]
+    batches += [(n, C.family(n), C.expected(n)) for n in C.EDGE_FAMILIES if n.startswith("size_edge")]
+    for name, lines, want in batches:
+        assert vcfc.encode_bound(len(lines), STRIDED_TOTAL) // 4096 + 1 >= 8192
+        for lead in (0, 1, 7, 15):
+            got = _device_encode_lines(torch, vcfc, lines, lead, total=STRIDED_TOTAL)
+            _check_records(vcfc, got, want, (name, lead))
+
+
+@pytest.mark.parametrize("name", ["size_edge_1024", "size_edge_2048", "size_edge_4096", "gdg_batch"])
+def test_output_capacity_at_every_record_boundary(torch, vcfc, name):
+    """out_cap from cap_values() (0, 1, 7, 8, every record boundary - 1 / 0 /
+    + 1, total - 1, total): the error word names the first row whose record
+    ends past out_cap (VCFC_E_NOSPACE) or is NO_ERROR, the records before that
+    row are the oracle's, and every byte at or past out_cap still holds 0xEE.
+    gdg_batch: GT:DP:GQ rows, deferred, whose out_cap report is held back."""
+    seed = C.SEEDED[name][1][0] if name in C.SEEDED else None
+    lines, want = C.family(name, seed), C.expected(name, seed)
+    sizes = [len(w) for w in want]
+    blob = b"".join(want)
+    for cap in C.cap_values(sizes):
+        out, rec, err = _device_encode_lines(torch, vcfc, lines, 3, cap=cap)
+        word, first = C.cap_expected(sizes, cap)
+        assert err == word, (name, cap, hex(err))
+        assert word == vcfc.NO_ERROR or (word & 0xFF) == vcfc.E_NOSPACE
+        k = sum(sizes[:first])
+        assert out[:k].cpu().numpy().tobytes() == blob[:k], (name, cap)
+        assert bool((out[cap:] == 0xEE).all()), (name, cap)
+
+
+@pytest.mark.parametrize("name", C.ERROR_BATCHES)
+def test_error_word_is_the_first_failing_row(torch, vcfc, name):
+    """error_batch(): d_err is exactly the first failing row's word (of
+    failing rows in three scan tiles and blocks: the atomic minimum), and the
+    output up to that row's offset is intact."""
+    lines, word, first = C.error_batch(name)
+    out, rec, err = _device_encode_lines(torch, vcfc, lines, 5)
+    assert err == word, (name, hex(err))
+    want = b"".join(G.oracle_encode_line(x)[1] for x in lines[:first])
+    assert int(rec[first]) == len(want)
+    assert out[:len(want)].cpu().numpy().tobytes() == want

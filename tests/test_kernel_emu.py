@@ -1,17 +1,28 @@
 """Kernel logic on the CPU: the product kernel source (csrc/vcfc_encode.hip)
 compiled against the fiber SIMT emulator (tests/simt_emu) and checked
-byte-exact against the oracle / the reference's golden vectors.  The GPU
-parity tests (test_gpu_encode.py) repeat these through the real HIP path."""
+byte-exact against the oracle / the reference's golden vectors.
+
+Shared with the GPU tests (test_gpu_encode.py): the rows.  encode_cases.py
+holds every row family of this file that is aimed at a kernel edge (the seeded
+ones that used to be built in the test bodies here, and the hand-built
+edge_rows()), the out_cap values and the error batches; the GPU tests run the
+same rows through the C ABI at every buffer alignment.  What only this file
+can check is the kernel path a row takes (E.LAST_RETRIES, E.last_deferred()):
+the path is a function of the row's bytes, so it is the same on the GPU.
+What only the GPU tests check is the order of the lanes' LDS accesses between
+two wave_sync()s (a fiber runs alone until the next collective), the counted
+vmcnt waits, the buffer loads' range clamp and the atomics across blocks."""
 import random
 
 import numpy as np
 import pytest
 
 import emu_io as E
+import encode_cases as C
 import golden_io as G
 
 
-def run(lines, lead=0):
+def run(lines, lead=0, cap=None, total=None):
     """Place lines in a buffer starting at `lead` (alignment sweep) and encode."""
     buf = bytearray(b"#" * lead)
     offs, lens = [], []
@@ -19,7 +30,7 @@ def run(lines, lead=0):
         offs.append(len(buf))
         lens.append(len(ln))
         buf += ln + b"\n"
-    return E.emu_encode(bytes(buf), np.array(offs, np.uint64), np.array(lens, np.uint32))
+    return E.emu_encode(bytes(buf), np.array(offs, np.uint64), np.array(lens, np.uint32), cap=cap, total=total)
 
 
 def test_edge_cases_all_alignments():
@@ -72,43 +83,17 @@ def test_random_vcf_rows_byte_exact():
 @pytest.mark.parametrize("seed", [1, 2, 3])
 def test_wide_rows_multi_chunk(seed):
     """Rows spanning many 1 KiB chunks, clean and with escapes/empty fields."""
-    rnd = random.Random(seed)
-    pfx = b"22\t16050075\trs1\tA\tG\t100\tPASS\t" + b"AF=0.1;" * rnd.randint(1, 300) + b"\tGT\t"
-    toks = []
-    for _ in range(rnd.randint(2000, 5000)):
-        r = rnd.random()
-        toks.append(b"0|0" if r < 0.85 else b"0|1" if r < 0.9 else b"1|1" if r < 0.95 else b"1|0" if r < 0.99 else b"2|1")
-    clean = pfx + b"\t".join(toks)
-    dirty = pfx + b"\t".join(toks[:100]) + b"\t\t" + b"\t".join(toks[100:])
-    runs = pfx + b"\t".join([b"0|0"] * 4000 + [b"1|1"] * 100)
-    lines = [clean, dirty, runs]
+    lines = C.wide_multi_chunk(seed)
     st, out, ro, err = run(lines, lead=seed)
     want = b"".join(G.oracle_encode_line(x)[1] for x in lines)
     assert err == (1 << 64) - 1 and out == want
-
-
-def _chr22_like_rows(n, samples, seed):
-    rnd = random.Random(seed)
-    rows = []
-    for i in range(n):
-        af = rnd.choice([0.0, 0.0005, 0.002, 0.01, 0.05, 0.3, 0.9])
-        multi = rnd.random() < 0.1
-        toks = []
-        for _ in range(samples):
-            a = [1 if rnd.random() < af else 0 for _ in range(2)]
-            if multi and rnd.random() < 0.01:
-                a[rnd.randint(0, 1)] = 2
-            toks.append(b"%d|%d" % (a[0], a[1]))
-        pfx = b"22\t%d\trs%d\tA\tG\t100\tPASS\tAC=1;AF=%.4f;NS=2504\tGT\t" % (16050075 + 32 * i, i, af)
-        rows.append(pfx + b"\t".join(toks))
-    return rows
 
 
 @pytest.mark.parametrize("seed", [11, 12])
 def test_chr22_like_rows_skip_path(seed):
     """Long 0|0 runs exercise the whole-chunk skip, 127-chunk boundaries that
     straddle chunks, and run transitions at chunk starts."""
-    lines = _chr22_like_rows(40, 2504, seed)
+    lines = C.chr22_like(seed)
     st, out, ro, err = run(lines, lead=seed % 16)
     assert err == (1 << 64) - 1
     assert E.LAST_RETRIES[0] == 0   # escapes stay on the fast kernel's general step
@@ -122,19 +107,7 @@ def test_short_rows_and_cap_boundaries(seed):
     runs whose lengths sit on and around the caps (31, 127) and the 256-slot
     chunk, at every class: the first/last-chunk masking and the in-lane
     full/pending byte rules."""
-    rnd = random.Random(seed)
-    classes = [b"0|0", b"0|1", b"1|0", b"1|1"]
-    lens = [1, 2, 3, 4, 5, 29, 30, 31, 32, 33, 61, 62, 63, 125, 126, 127, 128, 129, 253, 254, 255, 256, 257]
-    lines = []
-    for i in range(48):
-        toks = []
-        target = rnd.choice([1, 2, 3, 4, 5, 63, 64, 65, 255, 256, 257, 700, 1500])
-        while len(toks) < target:
-            c = rnd.choice(classes)
-            toks += [c] * rnd.choice(lens)
-        toks = toks[:target]
-        pfx = b"22\t%d\trs%d\tA\tG\t100\tPASS\t%s\tGT\t" % (100 + i, i, b"X" * rnd.randint(1, 40))
-        lines.append(pfx + b"\t".join(toks))
+    lines = C.caps(seed)
     for lead in (0, 1, 2, 3, 7, 13):
         st, out, ro, err = run(lines, lead=lead)
         assert err == (1 << 64) - 1
@@ -147,19 +120,7 @@ def test_short_rows_and_cap_boundaries(seed):
 def test_dense_rows_wrap_the_ring(seed):
     """Rows whose records are many times the 4 KiB LDS ring (a start at most
     tokens): run groups straddling the ring end, bursts every chunk."""
-    rnd = random.Random(seed)
-    classes = [b"0|0", b"0|1", b"1|0", b"1|1"]
-    lines = []
-    for i in range(6):
-        n = rnd.choice([9000, 17000, 24001])
-        p = rnd.choice([0.5, 0.9, 1.0])
-        toks, c = [], 0
-        for _ in range(n):
-            if rnd.random() < p:
-                c = rnd.randrange(4)
-            toks.append(classes[c])
-        pfx = b"22\t%d\trs%d\tA\tG\t100\tPASS\tAF=0.5\tGT\t" % (100 + i, i)
-        lines.append(pfx + b"\t".join(toks))
+    lines = C.ring_wrap(seed)
     for lead in (0, 5, 10):
         st, out, ro, err = run(lines, lead=lead)
         assert err == (1 << 64) - 1
@@ -175,26 +136,7 @@ def test_escape_rows_on_the_three_byte_path(seed):
     row end, in runs of escapes, and right after runs that end on the caps:
     the escape path of the fast kernel (esc8), with and without an escape as
     the incoming class of a chunk."""
-    rnd = random.Random(seed)
-    plain = [b"0|0", b"0|1", b"1|0", b"1|1"]
-    escs = [b"0|2", b"2|0", b"./.", b".|.", b"0/1", b"1/1", b"2|2", b"\xff|\x80", b"0|\r", b"3|1"]
-    lens = [1, 2, 30, 31, 32, 126, 127, 128, 511, 512, 513]
-    lines = []
-    for i in range(24):
-        target = rnd.choice([1, 2, 511, 512, 513, 1024, 1025, 2504, 5000])
-        dens = rnd.choice([0.0005, 0.01, 0.04, 0.3, 1.0])
-        toks = []
-        while len(toks) < target:
-            if rnd.random() < dens:
-                toks += [rnd.choice(escs)] * rnd.choice([1, 1, 1, 2, 5])
-            else:
-                toks += [rnd.choice(plain)] * rnd.choice(lens)
-        toks = toks[:target]
-        for p in rnd.sample([0, 510, 511, 512, 1023, 1024, target - 1], 3):
-            if 0 <= p < target:
-                toks[p] = rnd.choice(escs)
-        pfx = b"22\t%d\trs%d\tA\tG,T\t100\tPASS\t%s\tGT\t" % (100 + i, i, b"Y" * rnd.randint(1, 60))
-        lines.append(pfx + b"\t".join(toks))
+    lines = C.esc3(seed)
     for lead in (0, 3, 9):
         st, out, ro, err = run(lines, lead=lead)
         assert err == (1 << 64) - 1
@@ -276,37 +218,17 @@ def test_output_capacity_short():
         st2, out2, ro2, err2 = E.emu_encode(bytes(buf), np.array(offs, np.uint64), np.array(lens, np.uint32), cap=cap)
         assert err2 == (cut_row << 8) | 4, (cut_row, hex(err2))
         assert out2[:int(ro[cut_row])] == out[:int(ro[cut_row])]
+    # and at every record boundary - 1 / 0 / + 1 of the first 24 rows as a batch of their own
+    sizes = [int(ro[i + 1] - ro[i]) for i in range(24)]
+    for cap in C.cap_values(sizes):
+        st2, out2, ro2, err2 = run(lines[:24], cap=cap)
+        word, cut_row = C.cap_expected(sizes, cap)
+        assert err2 == word, (cap, hex(err2))
+        assert out2[:int(ro[cut_row])] == out[:int(ro[cut_row])]
 
 
-PFX_V = b"X\t100\trs1\tA\tG\t50\tPASS\tAC=1\tGT\t"
-
-
-def _var_rows(rnd, n, kinds):
-    """Rows of odd-length tokens (the variable-token kernel's shape)."""
-    rows = []
-    for i in range(n):
-        kind = kinds[i % len(kinds)]
-        S = rnd.choice([1, 2, 3, 17, 63, 64, 65, 200, 511, 512, 513, 1023, 1024, 1025, 1500, 2600])
-        toks = []
-        p00 = rnd.choice([0.0, 0.5, 0.9, 0.99, 1.0])
-        for j in range(S):
-            if kind == "hap":       # haploid beside diploid
-                toks.append(rnd.choice([b"0", b"1"]) if (j * 7 + i) % 3 == 0 else
-                            (b"0|0" if rnd.random() < p00 else rnd.choice([b"0|1", b"1|0", b"1|1", b"0|0"])))
-            elif kind == "dot":     # "." for missing
-                toks.append(b"." if rnd.random() < 0.2 else (b"0|0" if rnd.random() < p00 else
-                                                                  rnd.choice([b"0|1", b"1|1", b"2|1"])))
-            elif kind == "long":    # GT:DP:GQ and other odd lengths
-                toks.append(rnd.choice([b"0|0:35:99", b"0|1:17:12", b"1|1:123:9", b"0|0", b"1", b"./.",
-                                        b"0|0:1", b"0" * 41]))
-            elif kind == "gdg":     # escapes of 1, 5, 9 and 41 bytes only (the escape-chunk step)
-                toks.append(rnd.choice([b"0|0:35:99", b"0|1:17:12", b"1|1:123:9", b"0|0:1", b"1", b"0" * 41]))
-            elif kind == "ones":    # every token one byte
-                toks.append(rnd.choice([b"0", b"1", b"."]))
-            else:                   # plain runs with long 1-byte stretches
-                toks.append(b"0|0" if (j // 200) % 2 == 0 else b"1")
-        rows.append(PFX_V + b"\t".join(toks))
-    return rows
+# (the rows of the variable-token tests below: encode_cases.py has them)
+PFX_V, _var_rows, _gdg = C.PFX_V, C.var_rows, C.gdg
 
 
 @pytest.mark.parametrize("seed", [51, 52, 53])
@@ -459,11 +381,6 @@ def test_deferred_runs_share_tiles(monkeypatch):
         st, out, ro, err = run(lines, lead)
         assert err == (1 << 64) - 1 and E.last_deferred() == expect_defer
         assert out == b"".join(want), lead
-
-
-def _gdg(rnd, S):
-    return PFX_V + b"\t".join(b"%d|%d:%d:%d" % (rnd.randint(0, 1), rnd.randint(0, 1), rnd.randint(10, 99),
-                                             rnd.randint(10, 99)) for _ in range(S))
 
 
 def _encode_both(lines, monkeypatch, cap=None):
@@ -710,13 +627,7 @@ def test_escape_rows_ending_on_a_chunk_end(defer, monkeypatch):
     Byte-exact with and without deferred records, beside rows one half
     shorter and longer."""
     monkeypatch.setenv("EMU_DEFER", defer)
-    rnd = random.Random(2024)
-    lines = []
-    for S in (1023, 1024, 1025, 2047, 2048, 2049):
-        lines.append(PFX_V + b"\t".join(rnd.choice([b"0", b"1", b"."]) for _ in range(S)))
-    for S in (1023, 1024, 1025):
-        lines.append(PFX_V + b"\t".join(b"%d|%d:%d:%d" % (rnd.randint(0, 1), rnd.randint(0, 1), rnd.randint(10, 99),
-                                                         rnd.randint(10, 99)) for _ in range(S)))
+    lines = C.esc_chunk_end(2024)
     want = [G.oracle_encode_line(x)[1] for x in lines]
     for lead in (0, 5):
         st, out, ro, err = run(lines, lead)
@@ -735,41 +646,119 @@ def test_sparse_clean_ranges(seed):
     class crossing chunk ends inside a pending range, 0|0 gaps spanning whole
     chunks and 127-multiples, ranges cut by dense, escape and last chunks,
     and an event at token 0 (the first chunk's virtual run)."""
-    rnd = random.Random(seed)
-    classes = [b"0|1", b"1|0", b"1|1"]
-    lines = []
-    for i in range(16):
-        nch = rnd.choice([3, 5, 6, 9, 13])
-        toks = []
-        for c in range(nch):
-            kind = rnd.choice(["zero", "few", "edge", "edge", "dense", "esc", "run"])
-            chunk = [b"0|0"] * 512
-            if kind == "few":
-                for p in rnd.sample(range(512), rnd.choice([1, 2, 5, 20])):
-                    chunk[p] = rnd.choice(classes)
-            elif kind == "edge":
-                for p in rnd.sample(range(512), rnd.choice([61, 62, 63, 64, 65])):
-                    chunk[p] = rnd.choice(classes)
-            elif kind == "dense":
-                chunk = [rnd.choice(classes + [b"0|0"]) for _ in range(512)]
-            elif kind == "esc":
-                chunk[rnd.randrange(512)] = b"0|2"
-            elif kind == "run":   # one class from near the chunk end into the next chunk
-                cl = rnd.choice(classes)
-                for p in range(512 - rnd.randint(1, 40), 512):
-                    chunk[p] = cl
-                toks += chunk
-                chunk = [cl] * rnd.randint(1, 40) + [b"0|0"] * 600
-                chunk = chunk[:512]
-            toks += chunk
-        if rnd.random() < 0.5:
-            toks[0] = rnd.choice(classes)
-        toks = toks[:len(toks) - rnd.randrange(300)]
-        pfx = b"22\t%d\trs%d\tA\tG\t100\tPASS\t%s\tGT\t" % (100 + i, i, b"Z" * rnd.randint(1, 50))
-        lines.append(pfx + b"\t".join(toks))
+    lines = C.sparse_ranges(seed)
     for lead in (0, 6):
         st, out, ro, err = run(lines, lead=lead)
         assert err == (1 << 64) - 1
         assert E.LAST_RETRIES[0] == 0
         for i, ln in enumerate(lines):
             assert out[int(ro[i]):int(ro[i + 1])] == G.oracle_encode_line(ln)[1], (lead, i)
+
+
+def test_seeded_families_are_the_rows_they_were():
+    """The seeded families of encode_cases.py are byte for byte the rows this
+    file built in its test bodies before they moved (same seeds, same order
+    of draws): their digests, taken then."""
+    import hashlib
+    for (name, seed), want in C.SEEDED_SHA256.items():
+        got = hashlib.sha256(b"\n".join(C.family(name, seed))).hexdigest()[:16]
+        assert got == want, (name, seed)
+    assert {k for k in C.SEEDED_SHA256} == {(n, s) for n, s in C.all_families() if n in C.SEEDED and n != "gdg_batch"}
+
+
+# ---- the hand-built families of encode_cases.edge_rows() ---------------------
+
+EDGE_LEADS = (0, 1, 7, 15)
+
+
+def _check_rows(got, want, tag):
+    st, out, ro, err = got
+    assert err == C.NO_ERROR, (tag, hex(err))
+    o = 0
+    for i, w in enumerate(want):
+        assert int(ro[i]) == o and out[o:o + len(w)] == w, (tag, i)
+        o += len(w)
+    assert int(ro[len(want)]) == o == len(out), tag
+
+
+@pytest.mark.parametrize("lead", EDGE_LEADS)
+@pytest.mark.parametrize("name", C.EDGE_FAMILIES)
+def test_edge_rows(name, lead, monkeypatch):
+    """encode_cases.edge_rows(): prefixes ending around the prefix chunks and
+    the LDS ring and far past it with every token shape behind them, records
+    of k * 1024 + d bytes, cap-multiple runs ending at the chunk edges, chunks
+    of escapes only -- every record and offset equals the oracle's at buffer
+    alignments 0, 1, 7 and 15; the fast-shaped families never reach the
+    general path, those with rows for k_encode_var run with deferred records
+    off and on."""
+    lines, want = C.family(name), C.expected(name)
+    for defer in ("0", "1") if name in C.VAR_SHAPED else (None,):
+        if defer is not None:
+            monkeypatch.setenv("EMU_DEFER", defer)
+        _check_rows(run(lines, lead), want, (name, lead, defer))
+        if name in C.FAST_SHAPED:
+            assert E.LAST_RETRIES[0] == 0
+        if name == "prefix_edge_general":   # (an even-length token or an empty field in every row)
+            assert E.LAST_RETRIES[0] == len(lines)
+
+
+@pytest.mark.parametrize("base,pb", C.SIZE_BATCHES)
+def test_size_edge_both_primary_sizes(base, pb):
+    """Every size_edge batch with its records' first 1024 and first 2048
+    bytes in the primary staging (vcfc_prim_bytes: the other value by a
+    larger total_line_bytes or by short rows behind the batch): a record of
+    k * 1024 + d bytes ends d bytes off a burst, and the compaction's 16-byte
+    blocks cross record byte prim_bytes at every d."""
+    name = "size_edge_%d/%d" % (base, pb)
+    lines, total = C.size_edge_batch(base, pb)
+    n, tot = len(lines), sum(len(x) for x in lines) if total is None else total
+    assert C.prim_bytes(n, tot) == pb
+    want = [G.oracle_encode_line(x)[1] for x in lines]
+    for lead in (0, 7):
+        _check_rows(run(lines, lead, total=total), want, (name, lead))
+        assert E.LAST_RETRIES[0] == 0
+
+
+def test_size_edge_strided_compaction(monkeypatch):
+    """The compaction's strided grid (2 048 blocks over the tiles, chosen from
+    8 192 tiles on) on the size_edge records."""
+    monkeypatch.setenv("EMU_WIDE_COMPACT", "1")
+    for base in (1024, 4096):
+        name = "size_edge_%d" % base
+        _check_rows(run(C.family(name), 7), C.expected(name), name)
+
+
+@pytest.mark.parametrize("name", ["size_edge_1024", "size_edge_2048", "gdg_batch"])
+def test_output_capacity_at_every_record_boundary(name, monkeypatch):
+    """out_cap at encode_cases.cap_values(): 0, 1, 7, 8, every record
+    boundary - 1 / 0 / + 1, the total - 1 and the total -- the first row whose
+    record ends past out_cap is reported (or none), the records before it are
+    the oracle's, nothing is written at or past out_cap (emu_encode checks).
+    gdg_batch: deferred records and their held-back out_cap report."""
+    seed = C.SEEDED[name][1][0] if name in C.SEEDED else None
+    lines, want = C.family(name, seed), C.expected(name, seed)
+    sizes = [len(w) for w in want]
+    blob = b"".join(want)
+    for defer in ("0", "1") if name == "gdg_batch" else (None,):
+        if defer is not None:
+            monkeypatch.setenv("EMU_DEFER", defer)
+        for cap in C.cap_values(sizes):
+            st, out, ro, err = run(lines, 3, cap=cap)
+            word, first = C.cap_expected(sizes, cap)
+            assert err == word, (name, defer, cap, hex(err))
+            k = sum(sizes[:first])
+            assert out[:k] == blob[:k], (name, defer, cap)
+        if defer == "1":
+            assert E.last_deferred() > 0
+
+
+@pytest.mark.parametrize("name", C.ERROR_BATCHES)
+def test_error_batches(name):
+    """encode_cases.error_batch(): the error word is the first failing
+    row's (of failing rows in three scan tiles too), the output up to that
+    row's offset is intact."""
+    lines, word, first = C.error_batch(name)
+    st, out, ro, err = run(lines, 5)
+    assert err == word, (name, hex(err))
+    want = b"".join(G.oracle_encode_line(x)[1] for x in lines[:first])
+    assert int(ro[first]) == len(want) and out[:len(want)] == want
