@@ -624,6 +624,87 @@ int vcfc_genotype_counts_regions_buffer(vcfc_ctx *ctx, const uint8_t *in, uint64
 int vcfc_genotype_counts_regions_file(vcfc_ctx *ctx, const char *in_vcfc, const char *variants_tsv,
                                       const char *samples_tsv, const uint8_t *table, uint64_t table_bytes);
 
+/* ---- genotype matrix: export-bed (no reference action: the
+ * oracle is a per-token rule over the reference's own decode) ----------------
+ * The variants x samples matrix written out of the run-length code, one row
+ * per record.  Header, LEN hops, regular records, queries and the stop rules
+ * are those of genotype-counts above.  One total rule per decoded token, on
+ * the GT rule of genotype-counts (GT up to the first ':', split at every '|'
+ * and '/', a piece of digits is called with class min(2, value), every other
+ * piece is missing):
+ *   dosage (int8)   -1 if any piece is missing, else the number of pieces
+ *                   whose class is not 0, capped at 127
+ *   hap (int8 pair) hk = the class of piece k if it exists and is called,
+ *                   else -1; pieces past the second are ignored
+ *   bed (2 bits)    exactly two pieces, both called, both of class 0 or 1:
+ *                   0b11 for 0 and 0, 0b10 for one of each, 0b00 for 1 and 1;
+ *                   every other token 0b01 (missing).  PLINK 1 with A1 = ALT,
+ *                   A2 = REF.
+ * Row layouts, for S samples (vcfc_matrix_row_bytes; 0 for an unknown layout):
+ *   VCFC_GM_DOSAGE  S bytes, byte j = sample j
+ *   VCFC_GM_HAP     2 S bytes, bytes 2j and 2j + 1 = h0 and h1 of sample j
+ *   VCFC_GM_BED     ceil(S / 4) bytes, sample j in bits 2 (j mod 4) and
+ *                   2 (j mod 4) + 1 of byte j / 4; the unused high bits of the
+ *                   last byte are 0
+ *
+ * Device entry: the records d_in[d_rec_start[i], d_rec_start[i+1]), i < n <
+ * 2^32, read once; d_select nullable: records with d_select[i] == 0 get no
+ * row and are not checked.  d_row_of: n + 1 words, written on the device:
+ * d_row_of[i] = the selected records before i (i without d_select),
+ * d_row_of[n] = the number of rows.  The row of record i lies at d_out +
+ * d_row_of[i] * row_stride; its bytes [row_bytes, row_stride) and every other
+ * byte outside the rows are left untouched, for any stride and alignment.
+ * Asynchronous on `stream`, no host synchronisation; per-call state is reset
+ * by a kernel, so the call can be captured in a graph.  *d_err = ~0, or the
+ * minimum over records of (i << 8 | 3) for a selected record that is not
+ * regular (rows from i on are then not meaningful) and of (i << 8 | 0xFF) for
+ * a record whose row would end past out_cap: that record and later ones are
+ * not written, and nothing is ever written at or past d_out + out_cap.
+ * VCFC_E_ARG: an unknown layout, samples == 0 or >= 2^30, n >= 2^32,
+ * row_stride < row_bytes, a null d_out or d_row_of, ws_bytes below
+ * vcfc_matrix_workspace_size(n, samples, layout).  Up to 3 bytes past the
+ * last record's end must be readable.  vcfc_matrix_lds_samples(layout): the
+ * largest `samples` whose row is put together in LDS (above it a byte-serial
+ * path writes straight to global memory: correct, untuned). */
+#define VCFC_GM_DOSAGE 0
+#define VCFC_GM_HAP 1
+#define VCFC_GM_BED 2
+uint64_t vcfc_matrix_row_bytes(int layout, uint64_t samples);
+uint64_t vcfc_matrix_lds_samples(int layout);
+uint64_t vcfc_matrix_workspace_size(uint64_t n_records, uint64_t samples, int layout);
+int vcfc_genotype_matrix_device(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_rec_start,
+                                const uint8_t *d_select, uint64_t n, uint64_t samples, int layout, uint8_t *d_out,
+                                uint64_t out_cap, uint64_t row_stride, uint64_t *d_row_of, void *d_ws, uint64_t ws_bytes,
+                                uint64_t *d_err, void *stream);
+/* A whole .vcfc in host memory.  has_query == 0: every record (ref .. end are
+ * ignored).  rec_index[0, *n_rows) = the rows' records' file indices (room
+ * for rows_cap of them), rows = the matrix with row_stride = row_bytes (room
+ * for rows_bytes bytes), *n_samples = S.  VCFC_E_NOSPACE if either is short:
+ * *n_rows and *n_samples then give the sizes needed.  On VCFC_E_FORMAT the
+ * rows before the failing record are returned and *err_record is its file
+ * index (the record count where hopping stopped short).  The _regions entry
+ * takes a built table (vcfc_regions_build) in place of the region. */
+int vcfc_genotype_matrix_buffer(vcfc_ctx *ctx, const uint8_t *in, uint64_t in_bytes, int layout, int has_query,
+                                const char *ref, uint64_t ref_len, int has_range, uint64_t start, uint64_t end,
+                                uint64_t *rec_index, uint64_t rows_cap, uint8_t *rows, uint64_t rows_bytes,
+                                uint64_t *n_rows, uint64_t *n_samples, uint64_t *err_record);
+int vcfc_genotype_matrix_regions_buffer(vcfc_ctx *ctx, const uint8_t *in, uint64_t in_bytes, int layout,
+                                        const uint8_t *table, uint64_t table_bytes, uint64_t *rec_index, uint64_t rows_cap,
+                                        uint8_t *rows, uint64_t rows_bytes, uint64_t *n_rows, uint64_t *n_samples,
+                                        uint64_t *err_record);
+/* PLINK 1 files <out_prefix>.bed / .bim / .fam.  All three are opened
+ * (created, truncated) before the input is parsed.  .bed: the bytes 6C 1B 01,
+ * then the VCFC_GM_BED rows.  .bim: per row "CHROM\tID\t0\tPOS\tALT\tREF\n",
+ * REQ's TAB fields 0, 2, 1, 4, 3 verbatim.  .fam: per sample
+ * "name\tname\t0\t0\t0\t-9\n", the names verbatim from the '#CHROM' line.  On
+ * VCFC_E_FORMAT past the header .bed and .bim hold what precedes the failing
+ * record and .fam stays empty; a header that is refused leaves all three
+ * empty. */
+int vcfc_export_bed_file(vcfc_ctx *ctx, const char *in_vcfc, const char *out_prefix, int has_query, const char *ref,
+                         uint64_t ref_len, int has_range, uint64_t start, uint64_t end);
+int vcfc_export_bed_regions_file(vcfc_ctx *ctx, const char *in_vcfc, const char *out_prefix, const uint8_t *table,
+                                 uint64_t table_bytes);
+
 /* ---- sparse layout: sparsify_file (reference src/sparse.cpp:290-580) -------
  * Record i of the .vcfc goes to data_start + (300e6 + POS_i) * 16384
  * (compute_sparse_offset, src/sparse.cpp:18-51) behind a 16-byte prefix

@@ -1,0 +1,259 @@
+"""GPU parity for genotype-matrix: status, failing record,
+indices and rows of all three layouts against the Python restatement
+(matrix_cases.py, pinned to the oracle by test_matrix_emu.py) through the C
+ABI (libvcfc.so); the device entry on torch tensors, every byte of the output
+allocation outside the rows included; the three PLINK files of the file call
+and of the CLI (build/main) byte for byte; a 2504-sample file against a pack
+of a Python parse of its source VCF text; and the device call captured in a
+graph."""
+import io
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+import pytest
+
+import decode_cases as D
+import golden_io as G
+import matrix_cases as MC
+import regions_cases as RC
+import subset_cases as SC
+
+pytestmark = pytest.mark.gpu
+REPO = G.REPO
+sys.path.insert(0, os.path.join(REPO, "vcf-compression_amd"))
+MAIN = os.path.join(REPO, "build", "main")
+OK, E_ARG, E_FORMAT = MC.OK, MC.E_ARG, MC.E_FORMAT
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    import torch   # before libvcfc: one HIP runtime in the process
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    import vcfc
+    c = vcfc.Context(0)
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def run(ctx):
+    import vcfc
+
+    def f(data, layout, query=None, regions=None, rec_batch=0):
+        if layout not in MC.LAYOUTS:   # (numpy cannot shape the rows of an unknown layout)
+            pytest.fail("unknown layout")
+        st, idx, m = ctx.genotype_matrix_buffer(data, layout, None if query is None else vcfc.VcfCoordinateQuery(*query),
+                                                regions)
+        return st, [int(x) for x in idx], [r.tobytes() for r in m], None, ctx.last_matrix_record
+    return f
+
+
+def lds_samples(layout):
+    import vcfc
+    return vcfc.matrix_lds_samples(layout)
+
+
+def test_sizes():
+    import vcfc
+    assert [vcfc.matrix_row_bytes(k, 5) for k in (0, 1, 2, 3)] == [5, 10, 2, 0]
+    assert [lds_samples(k) for k in (0, 1, 2, 3)] == [5120, 2560, 4096, 0]
+    assert (vcfc.GM_DOSAGE, vcfc.GM_HAP, vcfc.GM_BED) == MC.LAYOUTS
+
+
+def test_valid_files(run):
+    MC.check_files(run, D.valid_files(1))
+
+
+def test_small_sample_counts(run):
+    MC.check_files(run, MC.small_files())
+
+
+def test_batch_files(run):
+    MC.check_files(run, SC.batch_files())
+
+
+def test_hand_built_records(run):
+    MC.check_hand_built(run)
+
+
+def test_irregular_records(run):
+    MC.check_irregular(run)
+
+
+@pytest.mark.parametrize("seed", [3, 4, 6])
+def test_mutated_files(run, seed):
+    MC.check_mutated(run, seed)
+
+
+def test_query_files(run):
+    MC.check_queries(run, 1)
+
+
+def test_region_tables(run):
+    MC.check_regions(run)
+
+
+def test_bad_headers(run, ctx):
+    data = D.valid_files(1)[2][1]
+    for layout in MC.LAYOUTS:
+        assert run(data[1:], layout)[:3] == (E_FORMAT, [], [])
+    s0 = next(d for n, d in D.mutated_files(3) if n == "S0_row")
+    assert run(s0, MC.BED)[0] == E_ARG
+    assert ctx.genotype_matrix_buffer(data, 3)[0] == E_ARG
+    st, idx, m = ctx.genotype_matrix_buffer(data, MC.DOSAGE)
+    assert m.dtype == np.int8 and ctx.genotype_matrix_buffer(data, MC.BED)[2].dtype == np.uint8
+    assert ctx.genotype_matrix_buffer(data, MC.HAP)[2].shape == (len(idx), 2 * m.shape[1])
+
+
+def device_run(body, rec, S, layout, select, row_stride, out_cap, alloc, ws_short=0, offset=0, null=None, n_override=None,
+               graph=False):
+    """vcfc_genotype_matrix_device on torch tensors, as matrix_cases' dev."""
+    import torch
+    import vcfc
+    n = len(rec) - 1
+    dev = "cuda:0"
+    d_in = torch.from_numpy(np.frombuffer(body + bytes(64), dtype=np.uint8).copy()).to(dev)
+    d_rec = torch.from_numpy(np.array(rec, dtype=np.int64)).to(dev)
+    d_sel = None if select is None else torch.from_numpy(np.array(select, dtype=np.uint8)).to(dev)
+    d_base = torch.full((offset + alloc + MC.CANARY,), MC.FILL, dtype=torch.uint8, device=dev)   # (256-byte aligned)
+    d_row_of = torch.full((n + 2,), -0x1111111111111112, dtype=torch.int64, device=dev)
+    wsb = vcfc.matrix_workspace_size(n, S, layout) - ws_short
+    d_ws = torch.full((wsb + 64,), 0xCD, dtype=torch.uint8, device=dev)
+    d_err = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def call(stream):
+        return vcfc.genotype_matrix_device(d_in.data_ptr(), len(body), d_rec.data_ptr(), None if d_sel is None else d_sel.data_ptr(),
+                                           n if n_override is None else n_override, S, layout,
+                                           None if null == "out" else d_base.data_ptr() + offset, out_cap, row_stride,
+                                           None if null == "row_of" else d_row_of.data_ptr(), d_ws.data_ptr(), wsb,
+                                           d_err.data_ptr(), stream)
+    if graph:
+        outs = []
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            st = call(torch.cuda.current_stream().cuda_stream)
+        for _ in range(2):
+            d_base.fill_(MC.FILL)
+            d_err.zero_()
+            d_row_of[:n + 1].fill_(7)
+            g.replay()
+            torch.cuda.synchronize()
+            outs.append((d_base.cpu().numpy().tobytes(), d_err.cpu().numpy().tobytes(), d_row_of[:n + 1].cpu().numpy().tobytes()))
+        assert outs[0] == outs[1], "two replays differ"
+    else:
+        st = call(torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    base = d_base.cpu().numpy()
+    row_of = d_row_of.cpu().numpy()
+    assert (base[:offset] == MC.FILL).all() and (d_ws[wsb:].cpu().numpy() == 0xCD).all(), "written before d_out / past the workspace"
+    assert st != OK or row_of[n + 1] == -0x1111111111111112
+    return st, int(d_err.cpu().numpy().view(np.uint64)[0]), base[offset:].tobytes(), [int(x) for x in row_of[:n + 1]]
+
+
+def test_device_entry():
+    MC.check_device(device_run)
+
+
+def test_device_entry_around_the_tile_limit(run):
+    MC.check_tile_limit(run, lds_samples)
+    MC.check_device_tile_limit(device_run, lds_samples)
+
+
+def test_device_entry_arguments():
+    import vcfc
+    MC.check_device_args(device_run, vcfc.matrix_workspace_size)
+
+
+def test_device_call_captured_in_a_graph():
+    name, data = MC.small_files()[6]
+    n = len(MC.records_of(data)[1]) - 1
+    for layout in MC.LAYOUTS:
+        for sel in (None, [int(i % 3 != 1) for i in range(n)]):
+            MC.check_device_call(lambda *a, **k: device_run(*a, graph=True, **k), data, layout, sel, lambda rb: rb + 1, offset=3)
+
+
+def cli(argv):
+    return subprocess.run([MAIN] + argv, capture_output=True, timeout=300)
+
+
+def read3(prefix):
+    return tuple(open(prefix + e, "rb").read() for e in (".bed", ".bim", ".fam"))
+
+
+def test_file_call_and_cli(ctx):
+    import vcfc
+    enc = G.gz("random_100x10000.vcfc.gz")
+    with tempfile.TemporaryDirectory() as d:
+        src, pre, reg = os.path.join(d, "t.vcfc"), os.path.join(d, "out"), os.path.join(d, "targets.bed")
+        with open(src, "wb") as f:
+            f.write(enc)
+        for region in (None, "1:10100-10300", "2"):
+            q = None if region is None else tuple(vcfc.parse_coordinate_string(region))
+            st, idx, rows, S, bad = MC.matrix(enc, MC.BED, q)
+            assert st == OK and (region == "2" or len(idx) > 0)
+            want = (MC.bed_file(rows), MC.bim_file(enc, idx), MC.fam_file(enc))
+            r = cli(["export-bed", src, pre] + ([] if region is None else [region]))
+            assert r.returncode == 0 and r.stdout == b"", r.stderr
+            assert read3(pre) == want, region
+            os.remove(pre + ".bed")
+            ctx.export_bed_file(src, pre, region)
+            assert read3(pre) == want, region
+        text = b"1\t10100\t10300\n1:10500-10550\n"
+        with open(reg, "wb") as f:
+            f.write(text)
+        st, idx, rows, S, bad = MC.matrix(enc, MC.BED, table=RC.parse_text(text))
+        assert st == OK and len(idx) > 0
+        want = (MC.bed_file(rows), MC.bim_file(enc, idx), MC.fam_file(enc))
+        r = cli(["export-bed-regions", src, pre, reg])
+        assert r.returncode == 0 and r.stdout == b"" and read3(pre) == want, r.stderr
+        ctx.export_bed_file(src, pre + "2", regions=text)
+        assert read3(pre + "2") == want
+        r = cli(["export-bed", src, pre, "1:5"])
+        assert r.returncode == 1 and r.stdout == (b"Query must contain a dash character: <ref>:<start>-<end>\n"
+                                                  b"Failed to parse query string: 1:5\n")
+        for argv in (["export-bed", src], ["export-bed-regions", src, pre], []):
+            r = cli(argv)
+            assert r.returncode == 1
+            assert b"./main export-bed <input_file> <output_prefix> [<ref>[:<start>-<end>]]\n" in r.stderr
+            assert b"./main export-bed-regions <input_file> <output_prefix> <regions-file>\n" in r.stderr
+        # a file that stops mid-way: exit 134, the rows before the stop, an empty .fam
+        name, bad_file = next(x for x in SC.query_files(1) if x[0] == "no_lf17")
+        with open(src, "wb") as f:
+            f.write(bad_file)
+        st, idx, rows, S, at = MC.matrix(bad_file, MC.BED)
+        assert (st, at, len(idx)) == (E_FORMAT, 17, 17)
+        r = cli(["export-bed", src, pre])
+        assert r.returncode == 134 and b"VcfValidationError" in r.stderr and vcfc.strerror(E_FORMAT).encode() in r.stderr
+        assert read3(pre) == (MC.bed_file(rows), MC.bim_file(bad_file, idx), b"")
+        with pytest.raises(RuntimeError, match=vcfc.strerror(E_FORMAT)):
+            ctx.export_bed_file(src, pre)
+        # a header the decoder refuses: all three files created, all empty
+        with open(src, "wb") as f:
+            f.write(enc[1:])
+        r = cli(["export-bed", src, pre])
+        assert r.returncode == 134 and read3(pre) == (b"", b"", b"")
+
+
+def test_file_2504_samples(ctx):
+    import random_vcf
+    buf = io.BytesIO()
+    random_vcf.generate(2504, 120, buf)
+    vcf = buf.getvalue()
+    enc = ctx.compress_buffer(vcf)
+    want = {layout: MC.matrix_of_vcf(vcf, layout) for layout in MC.LAYOUTS}
+    for layout in MC.LAYOUTS:
+        st, idx, m = ctx.genotype_matrix_buffer(enc, layout)
+        assert st == OK and idx.tolist() == list(range(120))
+        assert [r.tobytes() for r in m] == want[layout], layout
+    with tempfile.TemporaryDirectory() as d:
+        src, pre = os.path.join(d, "t.vcfc"), os.path.join(d, "p")
+        with open(src, "wb") as f:
+            f.write(enc)
+        ctx.export_bed_file(src, pre)
+        assert open(pre + ".bed", "rb").read() == MC.bed_file(want[MC.BED])
+    st, idx, m = ctx.genotype_matrix_buffer(enc, MC.DOSAGE, "1:%d-%d" % (10000 + 2 * 17, 10000 + 2 * 97))   # POS = 10000 + 2 i
+    assert st == OK and idx.tolist() == list(range(17, 98))
+    assert [r.tobytes() for r in m] == want[MC.DOSAGE][17:98]

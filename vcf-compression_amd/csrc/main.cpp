@@ -11,7 +11,9 @@
 // (DESIGN.md §4j), and the region lists: `main query-regions <in> <regions>`,
 // `main query-samples-regions <in> <regions> <names>` and
 // `main genotype-counts-regions <in> <variants.tsv> <samples.tsv> <regions>`
-// (DESIGN.md §4k).  Data lines are
+// (DESIGN.md §4k), and the PLINK 1 export: `main export-bed <in> <prefix>
+// [<query>]` and `main export-bed-regions <in> <prefix> <regions>`
+// (DESIGN.md §4l).  Data lines are
 // encoded on the GPU through libvcfc.so.  Error messages mirror the
 // reference's exceptions (which terminate the reference process).
 #include <cerrno>
@@ -40,7 +42,9 @@ static int usage() {
                     "./main genotype-counts <input_file> <variants.tsv> <samples.tsv> [<ref>[:<start>-<end>]]\n"
                     "./main query-regions <input_file> <regions-file>\n"
                     "./main query-samples-regions <input_file> <regions-file> <name>[,<name>...]\n"
-                    "./main genotype-counts-regions <input_file> <variants.tsv> <samples.tsv> <regions-file>\n");
+                    "./main genotype-counts-regions <input_file> <variants.tsv> <samples.tsv> <regions-file>\n"
+                    "./main export-bed <input_file> <output_prefix> [<ref>[:<start>-<end>]]\n"
+                    "./main export-bed-regions <input_file> <output_prefix> <regions-file>\n");
     return 1;
 }
 
@@ -584,6 +588,55 @@ int main(int argc, char **argv) {
         }
         if (st != VCFC_OK) {
             fprintf(stderr, "Error in %s of file: %s\n", counts ? "genotype-counts" : "decompression", vcfc_strerror(st));
+            return 1;
+        }
+        return 0;
+    }
+    if (action == "export-bed" || action == "export-bed-regions") {
+        // no reference counterpart: the genotype matrix as PLINK 1 <prefix>.bed / .bim / .fam
+        const bool regions = action == "export-bed-regions";
+        if (argc < (regions ? 5 : 4)) return usage();
+        std::vector<uint8_t> table;
+        if (regions && load_regions(argv[4], table)) return 1;   // before the input is opened
+        if (!file_exists(argv[2])) printf("Input file does not exist: %s\n", argv[2]);
+        for (const char *ext : {".bed", ".bim", ".fam"})
+            if (std::string(argv[3]) + ext == argv[2]) {
+                fprintf(stderr, "terminate called after throwing an instance of 'std::runtime_error'\n"
+                                "  what():  input and output file are the same\n");
+                return 134;
+            }
+        const bool query = !regions && argc > 4;
+        const std::string q(query ? argv[4] : "");
+        uint64_t ref_len = 0, start = 0, end = 0;
+        int has_range = 0;
+        if (query) {
+            const int pq = vcfc_parse_query(q.data(), q.size(), &ref_len, &has_range, &start, &end);
+            if (pq != 0) {
+                const size_t colon = q.find(':'), dash = q.find('-', colon + 1);
+                if (pq == 1) printf("Query must contain a dash character: <ref>:<start>-<end>\n");
+                else if (pq == 2) printf("Failed to parse int from start position: %s\n", q.substr(colon + 1, dash - colon - 1).c_str());
+                else printf("Failed to parse int from end position: %s\n", q.substr(dash + 1).c_str());
+                printf("Failed to parse query string: %s\n", q.c_str());
+                return 1;
+            }
+        }
+        vcfc_ctx *ctx = nullptr;
+        int st = vcfc_ctx_create(0, &ctx);
+        if (st != VCFC_OK) {
+            fprintf(stderr, "vcfc: %s\n", vcfc_strerror(st));
+            return 1;
+        }
+        fflush(stdout);
+        if (regions) st = vcfc_export_bed_regions_file(ctx, argv[2], argv[3], table.data(), table.size());
+        else st = vcfc_export_bed_file(ctx, argv[2], argv[3], query ? 1 : 0, q.data(), ref_len, has_range, start, end);
+        vcfc_ctx_destroy(ctx);
+        if (st == VCFC_E_FORMAT) {
+            fprintf(stderr, "terminate called after throwing an instance of 'VcfValidationError'\n"
+                            "  what():  %s\n", vcfc_strerror(st));
+            return 134;
+        }
+        if (st != VCFC_OK) {
+            fprintf(stderr, "Error in export-bed of file: %s\n", vcfc_strerror(st));
             return 1;
         }
         return 0;

@@ -25,6 +25,7 @@
 #include "vcfc_sparse_index_driver.h"
 #include "vcfc_subset_driver.h"
 #include "vcfc_counts_driver.h"
+#include "vcfc_matrix_driver.h"
 #include "vcfc_regions_driver.h"
 
 hipError_t vcfc_sparse_plan_launch(const uint8_t *recs, const uint64_t *rec_off, uint64_t n, uint64_t data_start,
@@ -1661,6 +1662,139 @@ int vcfc_genotype_counts_regions_file(vcfc_ctx *c, const char *in_path, const ch
                            [&](const MappedFile &f, vcfc_cnt::Result &R, uint64_t *data_off, uint64_t *S) {
                                CtxDecodeBuffers B(c);
                                return vcfc_cnt::counts_file(f.p, f.n, &match, B, c->stream, R, data_off, S);
+                           });
+}
+
+// ---- genotype matrix; driver in vcfc_matrix_driver.h -----------
+
+uint64_t vcfc_matrix_row_bytes(int layout, uint64_t samples) { return vcfc_matrix_row_size(layout, samples); }
+
+uint64_t vcfc_matrix_lds_samples(int layout) { return vcfc_matrix_tile_samples(layout); }
+
+uint64_t vcfc_matrix_workspace_size(uint64_t n_records, uint64_t, int) {
+    return vcfc_matrix_workspace_layout(n_records).total;
+}
+
+int vcfc_genotype_matrix_device(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_rec_start,
+                                const uint8_t *d_select, uint64_t n, uint64_t samples, int layout, uint8_t *d_out,
+                                uint64_t out_cap, uint64_t row_stride, uint64_t *d_row_of, void *d_ws, uint64_t ws_bytes,
+                                uint64_t *d_err, void *stream) {
+    return vcfc_gm::matrix_device(d_in, in_bytes, d_rec_start, d_select, n, samples, layout, d_out, out_cap, row_stride,
+                                  d_row_of, d_ws, ws_bytes, d_err, static_cast<hipStream_t>(stream));
+}
+
+namespace {
+// run(in, n, B, R, &data_off, &S): the matrix of a .vcfc by one of the two match steps
+using MatrixRun = std::function<int(const uint8_t *, uint64_t, vcfc_dec::Buffers &, vcfc_gm::Result &, uint64_t *, uint64_t *)>;
+
+// what the two genotype-matrix buffer entries hand back
+int matrix_to_caller(vcfc_ctx *c, const uint8_t *in, uint64_t n, int layout, uint64_t *rec_index, uint64_t rows_cap, uint8_t *rows, uint64_t rows_bytes,
+                     uint64_t *n_rows, uint64_t *n_samples, uint64_t *err_record, const MatrixRun &run) {
+    if (!c || (!in && n) || (!rec_index && rows_cap) || (!rows && rows_bytes) || !n_rows || !n_samples || !err_record) return VCFC_E_ARG;
+    *n_rows = *n_samples = 0;
+    *err_record = ~0ull;
+    if (!vcfc_matrix_row_size(layout, 1)) return VCFC_E_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
+    vcfc_gm::Result R;
+    uint64_t data_off = 0, S = 0;
+    CtxDecodeBuffers B(c);
+    const int st = run(in, n, B, R, &data_off, &S);
+    if (st != VCFC_OK && st != VCFC_E_FORMAT) return st;
+    *n_rows = R.index.size();
+    *n_samples = S;
+    *err_record = R.err_record;
+    if (*n_rows > rows_cap || R.rows.size() > rows_bytes) return VCFC_E_NOSPACE;
+    if (*n_rows) {
+        memcpy(rec_index, R.index.data(), 8 * R.index.size());
+        memcpy(rows, R.rows.data(), R.rows.size());
+    }
+    return st;
+}
+
+// the three files of an export-bed entry
+int matrix_to_files(vcfc_ctx *c, const char *in_path, const char *prefix, const MatrixRun &run) {
+    const std::string p(prefix);
+    int fd[3] = {-1, -1, -1};
+    static const char *const ext[3] = {".bed", ".bim", ".fam"};
+    for (int k = 0; k < 3; k++) {
+        fd[k] = open((p + ext[k]).c_str(), O_CREAT | O_TRUNC | O_WRONLY, 0644);
+        if (fd[k] < 0) {
+            while (k-- > 0) close(fd[k]);
+            return VCFC_E_IO;
+        }
+    }
+    MappedFile f;
+    int st = f.open_ro(in_path);
+    if (!st) {
+        vcfc_gm::Result R;
+        uint64_t data_off = 0, S = 0;
+        CtxDecodeBuffers B(c);
+        st = run(f.p, f.n, B, R, &data_off, &S);
+        if (data_off && S && (st == VCFC_OK || st == VCFC_E_FORMAT)) {   // past the header
+            std::vector<uint8_t> text;
+            vcfc_gm::render_bed(R, text);
+            if (write_all_at(fd[0], text.data(), text.size(), 0)) st = VCFC_E_IO;
+            vcfc_gm::render_bim(f.p + data_off, R, text);
+            if (write_all_at(fd[1], text.data(), text.size(), 0)) st = VCFC_E_IO;
+            if (st == VCFC_OK) {
+                vcfc_gm::render_fam(f.p, data_off, S, text);
+                if (write_all_at(fd[2], text.data(), text.size(), 0)) st = VCFC_E_IO;
+            }
+        }
+    }
+    for (int k = 0; k < 3; k++)
+        if (close(fd[k]) != 0 && !st) st = VCFC_E_IO;
+    return st;
+}
+}  // namespace
+
+int vcfc_genotype_matrix_buffer(vcfc_ctx *c, const uint8_t *in, uint64_t n, int layout, int has_query, const char *ref,
+                                uint64_t ref_len, int has_range, uint64_t start, uint64_t end, uint64_t *rec_index,
+                                uint64_t rows_cap, uint8_t *rows, uint64_t rows_bytes, uint64_t *n_rows,
+                                uint64_t *n_samples, uint64_t *err_record) {
+    if (has_query && !ref && ref_len) return VCFC_E_ARG;
+    const vcfc_gm::Query q{reinterpret_cast<const uint8_t *>(ref), ref_len, has_range, start, end};
+    return matrix_to_caller(c, in, n, layout, rec_index, rows_cap, rows, rows_bytes, n_rows, n_samples, err_record,
+                            [&](const uint8_t *p, uint64_t pn, vcfc_dec::Buffers &B, vcfc_gm::Result &R, uint64_t *data_off,
+                                uint64_t *S) {
+                                return vcfc_gm::matrix_file(p, pn, layout, has_query ? &q : nullptr, B, c->stream, R, data_off, S);
+                            });
+}
+
+int vcfc_genotype_matrix_regions_buffer(vcfc_ctx *c, const uint8_t *in, uint64_t n, int layout, const uint8_t *table,
+                                        uint64_t table_bytes, uint64_t *rec_index, uint64_t rows_cap, uint8_t *rows,
+                                        uint64_t rows_bytes, uint64_t *n_rows, uint64_t *n_samples, uint64_t *err_record) {
+    if (!vcfc_reg::regions_validate(table, table_bytes)) return VCFC_E_ARG;
+    const uint8_t *d_table = nullptr;
+    const vcfc_dec::MatchStep match = vcfc_reg::regions_step(table, table_bytes, &d_table);
+    return matrix_to_caller(c, in, n, layout, rec_index, rows_cap, rows, rows_bytes, n_rows, n_samples, err_record,
+                            [&](const uint8_t *p, uint64_t pn, vcfc_dec::Buffers &B, vcfc_gm::Result &R, uint64_t *data_off,
+                                uint64_t *S) { return vcfc_gm::matrix_file(p, pn, layout, &match, B, c->stream, R, data_off, S); });
+}
+
+int vcfc_export_bed_file(vcfc_ctx *c, const char *in_path, const char *prefix, int has_query, const char *ref,
+                         uint64_t ref_len, int has_range, uint64_t start, uint64_t end) {
+    if (!c || !in_path || !prefix || (has_query && !ref && ref_len)) return VCFC_E_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
+    const vcfc_gm::Query q{reinterpret_cast<const uint8_t *>(ref), ref_len, has_range, start, end};
+    return matrix_to_files(c, in_path, prefix,
+                           [&](const uint8_t *p, uint64_t pn, vcfc_dec::Buffers &B, vcfc_gm::Result &R, uint64_t *data_off,
+                               uint64_t *S) {
+                               return vcfc_gm::matrix_file(p, pn, VCFC_MATRIX_BED, has_query ? &q : nullptr, B, c->stream, R,
+                                                           data_off, S);
+                           });
+}
+
+int vcfc_export_bed_regions_file(vcfc_ctx *c, const char *in_path, const char *prefix, const uint8_t *table,
+                                 uint64_t table_bytes) {
+    if (!c || !in_path || !prefix || !vcfc_reg::regions_validate(table, table_bytes)) return VCFC_E_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
+    const uint8_t *d_table = nullptr;
+    const vcfc_dec::MatchStep match = vcfc_reg::regions_step(table, table_bytes, &d_table);
+    return matrix_to_files(c, in_path, prefix,
+                           [&](const uint8_t *p, uint64_t pn, vcfc_dec::Buffers &B, vcfc_gm::Result &R, uint64_t *data_off,
+                               uint64_t *S) {
+                               return vcfc_gm::matrix_file(p, pn, VCFC_MATRIX_BED, &match, B, c->stream, R, data_off, S);
                            });
 }
 

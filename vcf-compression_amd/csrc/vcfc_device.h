@@ -320,6 +320,58 @@ inline void vcfc_counts_args_workspace(VcfcCountsArgs &a, uint8_t *ws, const Vcf
 hipError_t vcfc_counts_run(const VcfcCountsArgs &a, hipStream_t s);
 
 // ---------------------------------------------------------------------------
+// Genotype matrix (vcfc_matrix.hip): per (selected) record one
+// row of the variants x samples matrix, written out of the run-length code:
+// int8 dosage, the two int8 haplotype planes interleaved, or PLINK 1 .bed
+// 2-bit codes.  A record that is not regular is reported in
+// err.
+#define VCFC_MATRIX_DOSAGE 0
+#define VCFC_MATRIX_HAP 1
+#define VCFC_MATRIX_BED 2
+struct VcfcMatrixArgs {
+    const uint8_t *in;          // data section bytes (device)
+    uint64_t n_bytes;
+    const uint64_t *rec_start;  // n + 1 record offsets into `in`
+    const uint8_t *select;      // nullptr, or per record: 0 = no row (not checked)
+    uint64_t n;                 // records (< 2^32)
+    uint64_t S;                 // samples declared by the header line (1 <= S < 2^30)
+    int layout;                 // VCFC_MATRIX_*
+    uint8_t *out;               // row r at out + r * row_stride; nothing at or past out + out_cap
+    uint64_t out_cap, row_stride;
+    uint64_t *row_of;           // n + 1 words: row_of[i] = selected records before i; row_of[n] = rows
+    // workspace (vcfc_matrix_workspace_layout)
+    uint32_t *flag32;           // the select flags as words (the scan's input)
+    uint64_t *partials;         // scan partials
+    uint32_t *seq_list;         // records left to the byte-serial path
+    uint32_t *seq_count;
+    uint64_t *err;              // min over records of (i << 8 | 3): not regular, (i << 8 | 0xFF): row past out_cap
+};
+// bytes of a row (0: unknown layout); constexpr: host and device
+constexpr uint64_t vcfc_matrix_row_size(int layout, uint64_t S) {
+    return layout == VCFC_MATRIX_DOSAGE ? S : layout == VCFC_MATRIX_HAP ? 2 * S : layout == VCFC_MATRIX_BED ? (S + 3) / 4 : 0;
+}
+// samples whose row fits the per-wave LDS tile k_gm_scan is built with
+// (5120 row bytes and their alignment slack; .bed: 4096 one-byte codes and
+// the packed row); above it the byte-serial kernel writes every row
+#define VCFC_MATRIX_TILE_BYTES 5136u
+constexpr uint64_t vcfc_matrix_tile_samples(int layout) {
+    return layout == VCFC_MATRIX_DOSAGE ? 5120u : layout == VCFC_MATRIX_HAP ? 2560u : layout == VCFC_MATRIX_BED ? 4096u : 0u;
+}
+struct VcfcMatrixLayout {
+    uint64_t flag32, partials, seq_list, seq_count, total;
+};
+VcfcMatrixLayout vcfc_matrix_workspace_layout(uint64_t n);
+inline void vcfc_matrix_args_workspace(VcfcMatrixArgs &a, uint8_t *ws, const VcfcMatrixLayout &L) {
+    a.flag32 = reinterpret_cast<uint32_t *>(ws + L.flag32);
+    a.partials = reinterpret_cast<uint64_t *>(ws + L.partials);
+    a.seq_list = reinterpret_cast<uint32_t *>(ws + L.seq_list);
+    a.seq_count = reinterpret_cast<uint32_t *>(ws + L.seq_count);
+}
+// row_of, then one pass over every (selected) record: its row, err (no host
+// synchronisation)
+hipError_t vcfc_matrix_run(const VcfcMatrixArgs &a, hipStream_t s);
+
+// ---------------------------------------------------------------------------
 // Range query (vcfc_decode.hip; reference query_compressed_file,
 // src/main.cpp:3777-3929).  `ref` is device memory.
 struct VcfcQuery {

@@ -59,6 +59,9 @@ EXPORTS = [
     "vcfc_query_regions_buffer", "vcfc_query_regions_file",
     "vcfc_query_samples_regions_buffer", "vcfc_query_samples_regions_file",
     "vcfc_genotype_counts_regions_buffer", "vcfc_genotype_counts_regions_file",
+    "vcfc_matrix_row_bytes", "vcfc_matrix_lds_samples", "vcfc_matrix_workspace_size", "vcfc_genotype_matrix_device",
+    "vcfc_genotype_matrix_buffer", "vcfc_genotype_matrix_regions_buffer", "vcfc_export_bed_file",
+    "vcfc_export_bed_regions_file",
 ]
 LINE_INDEX_HOP, LINE_INDEX_SCAN = 0, 1                       # include/vcfc.h VCFC_LINE_INDEX_*
 TRACE_INGEST, TRACE_DEVICE, TRACE_SPARSE_QUERY = 1, 2, 4     # include/vcfc.h VCFC_TRACE_*
@@ -151,13 +154,27 @@ def lib():
             "vcfc_query_samples_regions_file": [vp, ctypes.c_char_p, vp, u64, vp, u64, ctypes.c_int],
             "vcfc_genotype_counts_regions_buffer": [vp, vp, u64, vp, u64, vp, vp, u64, ctypes.POINTER(u64), vp, u64,
                                                     ctypes.POINTER(u64), ctypes.POINTER(u64)],
-            "vcfc_genotype_counts_regions_file": [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, vp, u64]}
+            "vcfc_genotype_counts_regions_file": [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, vp, u64],
+            # the genotype matrix
+            "vcfc_matrix_row_bytes": [ctypes.c_int, u64],
+            "vcfc_matrix_lds_samples": [ctypes.c_int],
+            "vcfc_matrix_workspace_size": [u64, u64, ctypes.c_int],
+            "vcfc_genotype_matrix_device": [vp, u64, vp, vp, u64, u64, ctypes.c_int, vp, u64, u64, vp, vp, u64, vp, vp],
+            "vcfc_genotype_matrix_buffer": [vp, vp, u64, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, u64, ctypes.c_int,
+                                            u64, u64, vp, u64, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(u64),
+                                            ctypes.POINTER(u64)],
+            "vcfc_genotype_matrix_regions_buffer": [vp, vp, u64, ctypes.c_int, vp, u64, vp, u64, vp, u64,
+                                                    ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)],
+            "vcfc_export_bed_file": [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, u64,
+                                     ctypes.c_int, u64, u64],
+            "vcfc_export_bed_regions_file": [vp, ctypes.c_char_p, ctypes.c_char_p, vp, u64]}
     for name, args in late.items():
         if hasattr(L, name):
             getattr(L, name).argtypes = args
     for name in ("vcfc_index_workspace_size", "vcfc_sparse_index_workspace_size", "vcfc_sparse_index_offset",
                  "vcfc_decode_sizes_workspace_size", "vcfc_subset_workspace_size", "vcfc_counts_workspace_size",
-                 "vcfc_counts_lds_samples", "vcfc_regions_workspace_size"):
+                 "vcfc_counts_lds_samples", "vcfc_regions_workspace_size", "vcfc_matrix_row_bytes",
+                 "vcfc_matrix_lds_samples", "vcfc_matrix_workspace_size"):
         if hasattr(L, name):
             getattr(L, name).restype = u64
     L.vcfc_record_hash_device.argtypes = [vp, vp, u64, vp, vp]
@@ -666,6 +683,62 @@ class Context:
         raise_for(_need("vcfc_genotype_counts_regions_file")(self._h, in_path.encode(), variants_path.encode(),
                                                              samples_path.encode(), tab.ctypes.data, len(tab)))
 
+    def genotype_matrix_buffer(self, data, layout, query=None, regions=None):
+        """genotype-matrix over .vcfc bytes: one row per record,
+        or per record matching `query` (a VcfCoordinateQuery or a coordinate
+        string) or `regions` (region text or a table from regions_build).
+        layout: GM_DOSAGE (int8[rows, S]), GM_HAP (int8[rows, 2 S]: h0, h1 per
+        sample) or GM_BED (uint8[rows, ceil(S / 4)], PLINK 1 codes).  Returns
+        (status, record_indices, matrix).  On VCFC_E_FORMAT the rows are those
+        before the failing record (`last_matrix_record`: its file index); any
+        other failure returns no rows."""
+        if query is not None and regions is not None:
+            raise ValueError("query and regions exclude each other")
+        if query is not None and not isinstance(query, VcfCoordinateQuery):
+            query = parse_coordinate_string(query)
+        src = np.frombuffer(data, dtype=np.uint8)
+        tab = np.frombuffer(_regions_table(regions), dtype=np.uint8) if regions is not None else None
+        ref = query.reference_name if query is not None else b""
+        cap, nbytes = len(data) // 12 + 16, max(4 * len(data), 4096)
+        while True:
+            idx, rows = np.zeros(cap, dtype=np.uint64), np.zeros(nbytes, dtype=np.uint8)
+            n, ns, bad = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+            if tab is not None:
+                st = _need("vcfc_genotype_matrix_regions_buffer")(
+                    self._h, src.ctypes.data, len(data), layout, tab.ctypes.data, len(tab), idx.ctypes.data, cap,
+                    rows.ctypes.data, nbytes, ctypes.byref(n), ctypes.byref(ns), ctypes.byref(bad))
+            else:
+                st = _need("vcfc_genotype_matrix_buffer")(
+                    self._h, src.ctypes.data, len(data), layout, int(query is not None), ref, len(ref),
+                    int(query.has_range) if query is not None else 0, query.start if query is not None else 0,
+                    query.end if query is not None else 0, idx.ctypes.data, cap, rows.ctypes.data, nbytes, ctypes.byref(n),
+                    ctypes.byref(ns), ctypes.byref(bad))
+            rb = matrix_row_bytes(layout, ns.value)
+            if st == E_NOSPACE and (n.value > cap or n.value * rb > nbytes):
+                cap, nbytes = max(cap, n.value), max(nbytes, n.value * rb)
+                continue
+            self.last_matrix_record = bad.value
+            m = rows[:n.value * rb].reshape(n.value, rb).copy()
+            return st, idx[:n.value].copy(), m if layout == GM_BED else m.view(np.int8)
+
+    def export_bed_file(self, in_path, prefix, query=None, regions=None):
+        """As `main export-bed <in.vcfc> <prefix> [<query>]` or, with
+        `regions`, `main export-bed-regions`: PLINK 1 <prefix>.bed / .bim / .fam."""
+        if query is not None and regions is not None:
+            raise ValueError("query and regions exclude each other")
+        if regions is not None:
+            tab = np.frombuffer(_regions_table(regions), dtype=np.uint8)
+            raise_for(_need("vcfc_export_bed_regions_file")(self._h, in_path.encode(), prefix.encode(), tab.ctypes.data,
+                                                            len(tab)))
+            return
+        if query is not None and not isinstance(query, VcfCoordinateQuery):
+            query = parse_coordinate_string(query)
+        ref = query.reference_name if query is not None else b""
+        raise_for(_need("vcfc_export_bed_file")(
+            self._h, in_path.encode(), prefix.encode(), int(query is not None), ref, len(ref),
+            int(query.has_range) if query is not None else 0, query.start if query is not None else 0,
+            query.end if query is not None else 0))
+
     def sparse_query_status(self, in_path, query):
         """query_sparse_file_fd (reference src/main.cpp:235-582) over a sparse
         file: (status, stdout bytes); E_FORMAT where the reference throws (the
@@ -1068,3 +1141,30 @@ def genotype_counts_device(d_in, in_bytes, d_rec_start, d_select, n, samples, d_
     Returns the status; enqueued on `stream`."""
     return _need("vcfc_genotype_counts_device")(d_in, in_bytes, d_rec_start, d_select, n, samples, d_variant, d_sample,
                                                 d_ws, ws_bytes, d_err, stream)
+
+
+GM_DOSAGE, GM_HAP, GM_BED = 0, 1, 2   # include/vcfc.h VCFC_GM_*
+
+
+def matrix_row_bytes(layout, samples):
+    """Bytes of a genotype-matrix row (0 for an unknown layout)."""
+    return int(_need("vcfc_matrix_row_bytes")(layout, samples))
+
+
+def matrix_lds_samples(layout):
+    """The largest sample count whose row the matrix kernel puts together in LDS."""
+    return int(_need("vcfc_matrix_lds_samples")(layout))
+
+
+def matrix_workspace_size(n_records, samples, layout):
+    return int(_need("vcfc_matrix_workspace_size")(n_records, samples, layout))
+
+
+def genotype_matrix_device(d_in, in_bytes, d_rec_start, d_select, n, samples, layout, d_out, out_cap, row_stride,
+                           d_row_of, d_ws, ws_bytes, d_err, stream=0):
+    """The genotype-matrix rows of device-resident records (include/vcfc.h
+    vcfc_genotype_matrix_device): record i's row at d_out + d_row_of[i] *
+    row_stride; d_select may be None.  Pointers or torch tensors' data_ptr().
+    Returns the status; enqueued on `stream`."""
+    return _need("vcfc_genotype_matrix_device")(d_in, in_bytes, d_rec_start, d_select, n, samples, layout, d_out, out_cap,
+                                                row_stride, d_row_of, d_ws, ws_bytes, d_err, stream)
