@@ -834,12 +834,16 @@ __device__ __forceinline__ bool esc8(const uint32_t (&d)[TPL8], int32_t t0, int3
 
 // Genotype chunk C (2 KiB) on the skip / clean / escape paths.  false = not
 // handled (nothing written): the chunk needs the general step.
+// INTERIOR: the caller knows that C is not the row's last chunk (the refill
+// loop of encode_fast, whose chunks have another one behind them): the copy
+// holds no last-chunk code.
+template <bool INTERIOR>
 __device__ __forceinline__ bool gt_step8(const Chunk8 &cur, uint32_t C, FastState &f, Ring &r) {
     const uint32_t l = vw::lane_id();
     const uint32_t T = f.T, phi = f.phi;
     constexpr uint32_t Z = 0x09307C30u;   // "0|0\t"
     const int32_t tf = (int32_t)(C * SLOTS8);
-    if (tf >= (int32_t)T) return true;
+    if (!INTERIOR && tf >= (int32_t)T) return true;
     uint32_t d[TPL8];
     const uint32_t ya = vw::shl1(cur.a.x, cur.y);   // look-ahead dword (see load_chunk)
 #pragma unroll
@@ -855,7 +859,7 @@ __device__ __forceinline__ bool gt_step8(const Chunk8 &cur, uint32_t C, FastStat
         return true;
     }
 #endif
-    if (tf + (int32_t)SLOTS8 < (int32_t)T) {
+    if (INTERIOR || tf + (int32_t)SLOTS8 < (int32_t)T) {
         // interior chunk: every slot a token, none of them the last.  After
         // a chunk with escapes the next one most likely has some too (the
         // random_vcf law: ~20 per chunk): test the escape shape alone.
@@ -942,7 +946,7 @@ __device__ bool encode_fast(const uint8_t *__restrict__ line, uint32_t len, Ring
     if (st >= 2) return false;
 
     // genotype phase: runs of clean chunks, three chunks in flight, broken
-    // by the (rare) chunks that need the general step.  The inner loop has a
+    // by the (rare) chunks that need the general step.  The refill loop has a
     // single exit (early exits merge into the latch and make hipcc's vmcnt
     // tracking fall back to vmcnt(0)); the general step sits outside it so
     // its registers do not add to the prefetch buffers'.
@@ -963,23 +967,43 @@ __device__ bool encode_fast(const uint8_t *__restrict__ line, uint32_t len, Ring
         vw::pin_loads();
         uint32_t C = C0, gen = C0;
         bool ok = true;
-        for (;;) {
-            if (ok) { ok = vw::readfirst(gt_step8(b0, C, f, r)); gen = C; }
-            // a row handed on at chunk 0 (esc8, f.hand = 2) loads nothing
-            // more: the loop's remaining loads go to an empty range (the same
-            // instructions, so the counted vmcnt waits stay as they are;
-            // unphased rows 7.06 -> 6.63 ms, profiles/r06/ab/ab_r6hn_*.txt)
-            rsG = f.hand == 2u ? rsZ : rsG;
-            b0 = load_chunk8(rsG, C + 3, lo32);
-            vw::pin_loads();
-            if (ok && C + 1 < ncG) { ok = vw::readfirst(gt_step8(b1, C + 1, f, r)); gen = C + 1; }
-            b1 = load_chunk8(rsG, C + 4, lo32);
-            vw::pin_loads();
-            if (ok && C + 2 < ncG) { ok = vw::readfirst(gt_step8(b2, C + 2, f, r)); gen = C + 2; }
-            b2 = load_chunk8(rsG, C + 5, lo32);
-            vw::pin_loads();
-            C = vw::readfirst(C + 3);
-            if (!ok || C >= ncG) break;
+        // Refill loop: entered only while chunk C + 3 exists, so every round
+        // of refills has a real chunk behind it and the three chunks it
+        // steps over are interior ones (C + 2 < ncG - 1).  A load past the
+        // row touches no memory but still takes its place in the vector
+        // memory queue and its return to the VGPRs: a 5-chunk row (2504
+        // samples) used to issue nine chunk loads, four of them past its
+        // end, and now issues six (headline k_encode 2.109 -> 2.034 ms,
+        // profiles/encode_tail/ab_law1.txt; DESIGN.md §4, "Load tail").
+        if (C + 3 < ncG) {
+            for (;;) {
+                ok = vw::readfirst(gt_step8<true>(b0, C, f, r));
+                gen = C;
+                // a row handed on at chunk 0 (esc8, f.hand = 2) loads nothing
+                // more: the loop's remaining loads go to an empty range (the same
+                // instructions, so the counted vmcnt waits stay as they are;
+                // unphased rows 7.06 -> 6.63 ms, profiles/r06/ab/ab_r6hn_*.txt)
+                rsG = f.hand == 2u ? rsZ : rsG;
+                b0 = load_chunk8(rsG, C + 3, lo32);
+                vw::pin_loads();
+                if (ok) { ok = vw::readfirst(gt_step8<true>(b1, C + 1, f, r)); gen = C + 1; }
+                b1 = load_chunk8(rsG, C + 4, lo32);
+                vw::pin_loads();
+                if (ok) { ok = vw::readfirst(gt_step8<true>(b2, C + 2, f, r)); gen = C + 2; }
+                b2 = load_chunk8(rsG, C + 5, lo32);
+                vw::pin_loads();
+                C = vw::readfirst(C + 3);
+                if (!ok || C + 3 >= ncG) break;
+            }
+        }
+        // The row's last one to three chunks (C < ncG <= C + 3): the buffers
+        // are consumed in order and nothing is loaded (a row handed on here,
+        // at chunk 0 of two or three, has no load left to redirect).
+        if (ok) {
+            ok = vw::readfirst(gt_step8<false>(b0, C, f, r));
+            gen = C;
+            if (ok && C + 1 < ncG) { ok = vw::readfirst(gt_step8<false>(b1, C + 1, f, r)); gen = C + 1; }
+            if (ok && C + 2 < ncG) { ok = vw::readfirst(gt_step8<false>(b2, C + 2, f, r)); gen = C + 2; }
         }
         if (ok) break;
         if (f.hand == 2u) {   // chunk 0 all escapes: k_encode_var's row, to be deferred (esc8)
