@@ -705,6 +705,78 @@ int vcfc_export_bed_file(vcfc_ctx *ctx, const char *in_vcfc, const char *out_pre
 int vcfc_export_bed_regions_file(vcfc_ctx *ctx, const char *in_vcfc, const char *out_prefix, const uint8_t *table,
                                  uint64_t table_bytes);
 
+/* ---- extract: extract-samples, extract-regions (no reference
+ * action: the oracle is the reference's own compress of the cut text) ----------
+ * A sample / region subset of a .vcfc, written as a .vcfc; no record becomes
+ * text.  `cols` as in the sample subset above (K >= 1 distinct columns < S, in
+ * output order); cols == NULL with n_cols == 0 means all S columns in file
+ * order.  The query is absent (has_query == 0), one region (matched exactly
+ * as vcfc_query_samples_buffer matches) or a region table (vcfc_regions_build;
+ * matched as vcfc_query_samples_regions_buffer matches).
+ * The header is always written: every '##' line verbatim, then the '#CHROM'
+ * line cut as the sample subset cuts it (verbatim with no column list).
+ * Records are found by LEN hops; without a query every record is taken, with
+ * one the matching records.  A taken record must be regular (the sample
+ * subset's definition) and re-encodable: REQ's first byte is neither TAB nor
+ * '#', REQ's last byte is TAB, REQ holds no two adjacent TABs, no chosen token
+ * is empty, and the output record's LEN fits its 30 bits.  The output record
+ * is exactly what the reference's compress writes for the line "REQ, chosen
+ * tokens joined by TAB, LF": REQ verbatim; the chosen tokens re-coded greedily
+ * in output order -- a token that spells 0|0 joins a run of up to 127, one
+ * that spells 0|1, 1|0 or 1|1 a run of up to 31, full bytes first and the
+ * remainder last, however the token was stored (an escape that spells a class
+ * joins the run; source runs made adjacent by the cut merge) --, every other
+ * token as 0xE1, its bytes and a TAB (none after the last chosen token); the
+ * LF; both 30-bit headers recomputed.  Output records are dense and in file
+ * order: header plus records is a valid .vcfc, and
+ *   output == compress(decompress-samples / query-samples of the input)
+ * whole bytes, for every accepted input.  The call stops with VCFC_E_FORMAT at
+ * the first taken record that is not regular or not re-encodable, at a match
+ * error, or where the LEN hops stop with 8 or more bytes left; the header and
+ * the records before that point are kept (a valid shorter .vcfc).
+ * VCFC_E_FORMAT with nothing written for a header the decoder refuses,
+ * VCFC_E_ARG with nothing written for a bad column list (as above; also S ==
+ * 0 with no list) or a bad region table.  Buffer variants: VCFC_E_NOSPACE if
+ * out_cap is short (*out_len = size needed).  File variants create / truncate
+ * out_vcfc before the input is parsed.
+ * vcfc_extract_bound: an upper bound on the output of n_records records cut
+ * to n_cols columns out of in_bytes of input (header included): in_bytes +
+ * n_records * (n_cols + 1) -- a chosen class token costs at most one run byte
+ * where it cost none of its own, any other chosen token its source bytes and
+ * terminator plus one, and the source's last token has no terminator. */
+uint64_t vcfc_extract_bound(uint64_t in_bytes, uint64_t n_records, uint64_t n_cols);
+int vcfc_extract_buffer(vcfc_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const uint32_t *cols, uint64_t n_cols,
+                        int has_query, const char *ref, uint64_t ref_len, int has_range, uint64_t start, uint64_t end,
+                        uint8_t *out, uint64_t out_cap, uint64_t *out_len);
+int vcfc_extract_file(vcfc_ctx *ctx, const char *in_vcfc, const char *out_vcfc, const uint32_t *cols, uint64_t n_cols,
+                      int has_query, const char *ref, uint64_t ref_len, int has_range, uint64_t start, uint64_t end);
+int vcfc_extract_regions_buffer(vcfc_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const uint32_t *cols,
+                                uint64_t n_cols, const uint8_t *table, uint64_t table_bytes, uint8_t *out,
+                                uint64_t out_cap, uint64_t *out_len);
+int vcfc_extract_regions_file(vcfc_ctx *ctx, const char *in_vcfc, const char *out_vcfc, const uint32_t *cols,
+                              uint64_t n_cols, const uint8_t *table, uint64_t table_bytes);
+/* Device-resident extract, exact in one call: the output records of records
+ * d_in[d_rec_start[i], d_rec_start[i+1]) (d_select nullable: records with
+ * d_select[i] == 0 are not taken and not checked) at d_out + d_rec_off[i];
+ * d_rec_off[n] = total (n + 1 offsets).  `cols` as in
+ * vcfc_decode_samples_device (NULL with n_cols == 0: all `samples` columns);
+ * the same upload, synchronisation and 3 readable bytes past the last record.
+ * A wave re-codes a record whose n_cols <= VCFC_EXTRACT_TILE_COLS (4096)
+ * chosen columns fit its LDS tile; above that, and for records that are
+ * regular but not simple (long or multi-token escapes, zero counts, an
+ * LF-ended last token, more than 248 chosen other tokens), a byte-serial lane
+ * does.  *d_err = ~0, or min over records of (i << 8 | 3): not regular, (i <<
+ * 8 | 5): regular but not re-encodable (either way it and the records after it
+ * have no meaningful output), (i << 8 | 0xFF): out_cap too small.
+ * vcfc_extract_workspace_size takes the number of chosen columns (`samples`
+ * where all are chosen). */
+#define VCFC_EXTRACT_TILE_COLS 4096
+uint64_t vcfc_extract_workspace_size(uint64_t n_records, uint64_t n_cols);
+int vcfc_extract_samples_device(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_rec_start,
+                                const uint8_t *d_select, uint64_t n, uint64_t samples, const uint32_t *cols,
+                                uint64_t n_cols, uint8_t *d_out, uint64_t out_cap, uint64_t *d_rec_off, void *d_ws,
+                                uint64_t ws_bytes, uint64_t *d_err, void *stream);
+
 /* ---- sparse layout: sparsify_file (reference src/sparse.cpp:290-580) -------
  * Record i of the .vcfc goes to data_start + (300e6 + POS_i) * 16384
  * (compute_sparse_offset, src/sparse.cpp:18-51) behind a 16-byte prefix

@@ -24,6 +24,7 @@
 #include "vcfc_ingest_driver.h"
 #include "vcfc_sparse_index_driver.h"
 #include "vcfc_subset_driver.h"
+#include "vcfc_extract_driver.h"
 #include "vcfc_counts_driver.h"
 #include "vcfc_matrix_driver.h"
 #include "vcfc_regions_driver.h"
@@ -1630,6 +1631,120 @@ int vcfc_query_samples_regions_file(vcfc_ctx *c, const char *in_path, const uint
     CtxDecodeBuffers B(c);
     return vcfc_sub::matched_section(f.p + sc.data_off, f.n - sc.data_off, sc.S, sc.csort, sc.rank,
                                      vcfc_reg::regions_step(table, table_bytes, &d_table), B, c->stream, FdSink{out_fd});
+}
+
+// ---- extract; driver in vcfc_extract_driver.h ---------------------
+
+uint64_t vcfc_extract_bound(uint64_t in_bytes, uint64_t n_records, uint64_t n_cols) {
+    return vcfc_ext::extract_bound(in_bytes, n_records, n_cols);
+}
+
+namespace {
+// header (sunk first) and records of an extract of host bytes in[0, n)
+int extract_run(vcfc_ctx *c, const uint8_t *in, uint64_t n, const uint32_t *cols, uint64_t n_cols,
+                const vcfc_dec::MatchStep *match, const vcfc_dec::Sink &sink) {
+    vcfc_ext::Call ec;
+    const int st = ec.prepare(in, n, cols, n_cols);
+    if (st) return st;   // nothing written
+    if (!sink(ec.hdr.data(), ec.hdr.size())) return VCFC_E_IO;
+    CtxDecodeBuffers B(c);
+    return vcfc_ext::extract_section(in + ec.data_off, n - ec.data_off, ec.S, ec.csort, ec.rank, match, B, c->stream, sink);
+}
+
+int extract_to_buffer(vcfc_ctx *c, const uint8_t *in, uint64_t n, const uint32_t *cols, uint64_t n_cols,
+                      const vcfc_dec::MatchStep *match, uint8_t *out, uint64_t out_cap, uint64_t *out_len) {
+    *out_len = 0;
+    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
+    BufferSink bs{out, out_cap};
+    const int st = extract_run(c, in, n, cols, n_cols, match, std::ref(bs));
+    *out_len = bs.o;
+    return bs.fits ? st : VCFC_E_NOSPACE;
+}
+
+// (the output is created before the input is parsed)
+int extract_to_file(vcfc_ctx *c, const char *in_path, const char *out_path, const uint32_t *cols, uint64_t n_cols,
+                    const vcfc_dec::MatchStep *match) {
+    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
+    MappedFile f;
+    int st = f.open_ro(in_path);
+    if (st) return st;
+    const int fd = open(out_path, O_CREAT | O_TRUNC | O_WRONLY, 0644);
+    if (fd < 0) return VCFC_E_IO;
+    st = extract_run(c, f.p, f.n, cols, n_cols, match, FdSink{fd});
+    if (close(fd) != 0 && !st) st = VCFC_E_IO;
+    return st;
+}
+}  // namespace
+
+int vcfc_extract_buffer(vcfc_ctx *c, const uint8_t *in, uint64_t n, const uint32_t *cols, uint64_t n_cols, int has_query,
+                        const char *ref, uint64_t ref_len, int has_range, uint64_t start, uint64_t end, uint8_t *out,
+                        uint64_t out_cap, uint64_t *out_len) {
+    if (!c || (!in && n) || (has_query && !ref && ref_len) || (!out && out_cap) || !out_len) return VCFC_E_ARG;
+    if (has_query && ref_len > 0xFFFFFFFFull) return VCFC_E_FORMAT;
+    VcfcQuery q;
+    const vcfc_dec::MatchStep m =
+        vcfc_dec::region_step(reinterpret_cast<const uint8_t *>(ref), has_query ? ref_len : 0, has_range, start, end, &q);
+    return extract_to_buffer(c, in, n, cols, n_cols, has_query ? &m : nullptr, out, out_cap, out_len);
+}
+
+int vcfc_extract_file(vcfc_ctx *c, const char *in_path, const char *out_path, const uint32_t *cols, uint64_t n_cols,
+                      int has_query, const char *ref, uint64_t ref_len, int has_range, uint64_t start, uint64_t end) {
+    if (!c || !in_path || !out_path || (has_query && !ref && ref_len)) return VCFC_E_ARG;
+    if (has_query && ref_len > 0xFFFFFFFFull) return VCFC_E_FORMAT;
+    VcfcQuery q;
+    const vcfc_dec::MatchStep m =
+        vcfc_dec::region_step(reinterpret_cast<const uint8_t *>(ref), has_query ? ref_len : 0, has_range, start, end, &q);
+    return extract_to_file(c, in_path, out_path, cols, n_cols, has_query ? &m : nullptr);
+}
+
+int vcfc_extract_regions_buffer(vcfc_ctx *c, const uint8_t *in, uint64_t n, const uint32_t *cols, uint64_t n_cols,
+                                const uint8_t *table, uint64_t table_bytes, uint8_t *out, uint64_t out_cap,
+                                uint64_t *out_len) {
+    if (!c || (!in && n) || (!out && out_cap) || !out_len || !vcfc_reg::regions_validate(table, table_bytes))
+        return VCFC_E_ARG;
+    const uint8_t *d_table = nullptr;
+    const vcfc_dec::MatchStep m = vcfc_reg::regions_step(table, table_bytes, &d_table);
+    return extract_to_buffer(c, in, n, cols, n_cols, &m, out, out_cap, out_len);
+}
+
+int vcfc_extract_regions_file(vcfc_ctx *c, const char *in_path, const char *out_path, const uint32_t *cols,
+                              uint64_t n_cols, const uint8_t *table, uint64_t table_bytes) {
+    if (!c || !in_path || !out_path || !vcfc_reg::regions_validate(table, table_bytes)) return VCFC_E_ARG;
+    const uint8_t *d_table = nullptr;
+    const vcfc_dec::MatchStep m = vcfc_reg::regions_step(table, table_bytes, &d_table);
+    return extract_to_file(c, in_path, out_path, cols, n_cols, &m);
+}
+
+static_assert(VCFC_EXTRACT_TILE_COLS == VCFC_EXTRACT_TILE, "include/vcfc.h states the kernels' tile limit");
+
+uint64_t vcfc_extract_workspace_size(uint64_t n_records, uint64_t n_cols) {
+    return vcfc_extract_workspace_layout(n_records, n_cols).total;
+}
+
+int vcfc_extract_samples_device(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_rec_start,
+                                const uint8_t *d_select, uint64_t n, uint64_t samples, const uint32_t *cols,
+                                uint64_t n_cols, uint8_t *d_out, uint64_t out_cap, uint64_t *d_rec_off, void *d_ws,
+                                uint64_t ws_bytes, uint64_t *d_err, void *stream) {
+    if ((n && (!d_in || !d_rec_start || (!d_out && out_cap))) || !d_ws || !d_rec_off || !d_err) return VCFC_E_ARG;
+    std::vector<uint32_t> csort, rank;
+    if (vcfc_ext::device_columns(cols, n_cols, samples, csort, rank)) return VCFC_E_ARG;
+    const uint64_t K = csort.size();
+    const VcfcSubsetLayout L = vcfc_extract_workspace_layout(n, K);
+    if (ws_bytes < L.total) return VCFC_E_NOSPACE;
+    uint8_t *ws = static_cast<uint8_t *>(d_ws);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    VcfcExtractArgs a;
+    a.in = d_in; a.n_bytes = in_bytes; a.rec_start = d_rec_start; a.select = d_select; a.n = n; a.S = samples;
+    a.K = (uint32_t)K; a.out = d_out; a.out_cap = out_cap; a.line_off = d_rec_off;
+    vcfc_subset_args_workspace(a, ws, L);
+    a.err = d_err;
+    // csort and rank live on this frame: the stream has taken them when the synchronise returns
+    if (hipMemcpyAsync(ws + L.csort, csort.data(), 4 * K, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(ws + L.rank, rank.data(), 4 * K, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return VCFC_E_HIP;
+    if (vcfc_extract_plan(a, s) != hipSuccess) return VCFC_E_HIP;
+    return vcfc_extract_write(a, 0, n, s) == hipSuccess ? VCFC_OK : VCFC_E_HIP;
 }
 
 int vcfc_genotype_counts_regions_buffer(vcfc_ctx *c, const uint8_t *in, uint64_t n, const uint8_t *table,

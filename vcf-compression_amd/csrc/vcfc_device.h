@@ -279,6 +279,22 @@ hipError_t vcfc_subset_plan(const VcfcSubsetArgs &a, hipStream_t s);
 hipError_t vcfc_subset_write(const VcfcSubsetArgs &a, uint64_t first, uint64_t last, hipStream_t s);
 
 // ---------------------------------------------------------------------------
+// Extract (vcfc_extract.hip): REQ and K chosen sample columns of
+// every record, as a .vcfc record again.  The subset decoder's argument block
+// and workspace arrays, read as: out = records, line_size / line_off = record
+// sizes / offsets, seq_scratch = 2 * VCFC_EXTRACT_SEQ_LANES * K words, err
+// codes 3 = not regular, 5 = regular but not re-encodable, 0xFF = out_cap short.
+typedef VcfcSubsetArgs VcfcExtractArgs;
+#define VCFC_EXTRACT_SEQ_LANES 1024u
+// chosen columns the wave path's LDS tile holds; above it every record takes the byte-serial path
+#define VCFC_EXTRACT_TILE 4096u
+VcfcSubsetLayout vcfc_extract_workspace_layout(uint64_t n, uint64_t K);
+// exact plan: statuses, record sizes, record offsets, err (no host synchronisation)
+hipError_t vcfc_extract_plan(const VcfcExtractArgs &a, hipStream_t s);
+// write records [first, last) at a.out + line_off[i] (after vcfc_extract_plan)
+hipError_t vcfc_extract_write(const VcfcExtractArgs &a, uint64_t first, uint64_t last, hipStream_t s);
+
+// ---------------------------------------------------------------------------
 // Genotype counts (vcfc_counts.hip): per record a row of eight
 // counters, per sample five, both taken from the run-length code without
 // decoding it.  A record that is not regular is reported in

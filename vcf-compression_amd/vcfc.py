@@ -62,6 +62,8 @@ EXPORTS = [
     "vcfc_matrix_row_bytes", "vcfc_matrix_lds_samples", "vcfc_matrix_workspace_size", "vcfc_genotype_matrix_device",
     "vcfc_genotype_matrix_buffer", "vcfc_genotype_matrix_regions_buffer", "vcfc_export_bed_file",
     "vcfc_export_bed_regions_file",
+    "vcfc_extract_bound", "vcfc_extract_workspace_size", "vcfc_extract_samples_device", "vcfc_extract_buffer",
+    "vcfc_extract_file", "vcfc_extract_regions_buffer", "vcfc_extract_regions_file",
 ]
 LINE_INDEX_HOP, LINE_INDEX_SCAN = 0, 1                       # include/vcfc.h VCFC_LINE_INDEX_*
 TRACE_INGEST, TRACE_DEVICE, TRACE_SPARSE_QUERY = 1, 2, 4     # include/vcfc.h VCFC_TRACE_*
@@ -167,14 +169,25 @@ def lib():
                                                     ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)],
             "vcfc_export_bed_file": [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, u64,
                                      ctypes.c_int, u64, u64],
-            "vcfc_export_bed_regions_file": [vp, ctypes.c_char_p, ctypes.c_char_p, vp, u64]}
+            "vcfc_export_bed_regions_file": [vp, ctypes.c_char_p, ctypes.c_char_p, vp, u64],
+            # extract
+            "vcfc_extract_bound": [u64, u64, u64],
+            "vcfc_extract_workspace_size": [u64, u64],
+            "vcfc_extract_samples_device": [vp, u64, vp, vp, u64, u64, vp, u64, vp, u64, vp, vp, u64, vp, vp],
+            "vcfc_extract_buffer": [vp, vp, u64, vp, u64, ctypes.c_int, ctypes.c_char_p, u64, ctypes.c_int, u64, u64, vp,
+                                    u64, ctypes.POINTER(u64)],
+            "vcfc_extract_file": [vp, ctypes.c_char_p, ctypes.c_char_p, vp, u64, ctypes.c_int, ctypes.c_char_p, u64,
+                                  ctypes.c_int, u64, u64],
+            "vcfc_extract_regions_buffer": [vp, vp, u64, vp, u64, vp, u64, vp, u64, ctypes.POINTER(u64)],
+            "vcfc_extract_regions_file": [vp, ctypes.c_char_p, ctypes.c_char_p, vp, u64, vp, u64]}
     for name, args in late.items():
         if hasattr(L, name):
             getattr(L, name).argtypes = args
     for name in ("vcfc_index_workspace_size", "vcfc_sparse_index_workspace_size", "vcfc_sparse_index_offset",
                  "vcfc_decode_sizes_workspace_size", "vcfc_subset_workspace_size", "vcfc_counts_workspace_size",
                  "vcfc_counts_lds_samples", "vcfc_regions_workspace_size", "vcfc_matrix_row_bytes",
-                 "vcfc_matrix_lds_samples", "vcfc_matrix_workspace_size"):
+                 "vcfc_matrix_lds_samples", "vcfc_matrix_workspace_size", "vcfc_extract_bound",
+                 "vcfc_extract_workspace_size"):
         if hasattr(L, name):
             getattr(L, name).restype = u64
     L.vcfc_record_hash_device.argtypes = [vp, vp, u64, vp, vp]
@@ -739,6 +752,64 @@ class Context:
             int(query.has_range) if query is not None else 0, query.start if query is not None else 0,
             query.end if query is not None else 0))
 
+    def extract_buffer(self, data, cols=None, query=None, regions=None, cap=None):
+        """extract: the 0-based sample columns `cols` (None:
+        all) of the records `query` or `regions` match (neither: all), as a
+        .vcfc again.  Returns (status, bytes): on VCFC_E_FORMAT the bytes are
+        the header and the records before the first one that is not regular
+        or not re-encodable, a valid shorter .vcfc; VCFC_E_ARG (bad columns, a
+        bad table) writes nothing."""
+        if query is not None and regions is not None:
+            raise ValueError("query and regions exclude each other")
+        src = np.frombuffer(data, dtype=np.uint8)
+        c = None if cols is None else np.asarray(cols, dtype=np.uint32)
+        cp, k = (None, 0) if c is None else (c.ctypes.data, len(c))
+        if c is not None and k == 0:
+            cp = np.zeros(1, dtype=np.uint32).ctypes.data   # an empty list is not "all columns"
+        tab = np.frombuffer(_regions_table(regions), dtype=np.uint8) if regions is not None else None
+        if query is not None and not isinstance(query, VcfCoordinateQuery):
+            query = parse_coordinate_string(query)
+        cap = cap if cap is not None else len(data) + 4096
+        while True:
+            out = np.empty(max(cap, 1), dtype=np.uint8)
+            n = ctypes.c_uint64(0)
+            if tab is not None:
+                st = _need("vcfc_extract_regions_buffer")(self._h, src.ctypes.data, len(data), cp, k, tab.ctypes.data,
+                                                          len(tab), out.ctypes.data, cap, ctypes.byref(n))
+            else:
+                ref = query.reference_name if query is not None else b""
+                st = _need("vcfc_extract_buffer")(
+                    self._h, src.ctypes.data, len(data), cp, k, int(query is not None), ref, len(ref),
+                    int(query.has_range) if query is not None else 0, query.start if query is not None else 0,
+                    query.end if query is not None else 0, out.ctypes.data, cap, ctypes.byref(n))
+            if st == E_NOSPACE and n.value > cap:
+                cap = n.value
+                continue
+            return st, out[:n.value].tobytes()
+
+    def extract_file(self, in_path, out_path, cols=None, query=None, regions=None):
+        """As `main extract-samples <in> <out> <names> [<query>]` or, with
+        `regions`, `main extract-regions <in> <out> <regions> [<names>]`, with
+        columns in place of names."""
+        if query is not None and regions is not None:
+            raise ValueError("query and regions exclude each other")
+        c = None if cols is None else np.asarray(cols, dtype=np.uint32)
+        cp, k = (None, 0) if c is None else (c.ctypes.data, len(c))
+        if c is not None and k == 0:
+            cp = np.zeros(1, dtype=np.uint32).ctypes.data
+        if regions is not None:
+            tab = np.frombuffer(_regions_table(regions), dtype=np.uint8)
+            raise_for(_need("vcfc_extract_regions_file")(self._h, in_path.encode(), out_path.encode(), cp, k,
+                                                         tab.ctypes.data, len(tab)))
+            return
+        if query is not None and not isinstance(query, VcfCoordinateQuery):
+            query = parse_coordinate_string(query)
+        ref = query.reference_name if query is not None else b""
+        raise_for(_need("vcfc_extract_file")(
+            self._h, in_path.encode(), out_path.encode(), cp, k, int(query is not None), ref, len(ref),
+            int(query.has_range) if query is not None else 0, query.start if query is not None else 0,
+            query.end if query is not None else 0))
+
     def sparse_query_status(self, in_path, query):
         """query_sparse_file_fd (reference src/main.cpp:235-582) over a sparse
         file: (status, stdout bytes); E_FORMAT where the reference throws (the
@@ -1122,6 +1193,29 @@ def decode_samples_device(d_in, in_bytes, d_rec_start, d_select, n, samples, col
     c = np.asarray(cols, dtype=np.uint32)
     return _need("vcfc_decode_samples_device")(d_in, in_bytes, d_rec_start, d_select, n, samples, c.ctypes.data, len(c),
                                                d_out, out_cap, d_line_off, d_ws, ws_bytes, d_err, stream)
+
+
+def extract_bound(in_bytes, n_records, n_cols):
+    return int(_need("vcfc_extract_bound")(in_bytes, n_records, n_cols))
+
+
+def extract_workspace_size(n_records, n_cols):
+    """n_cols: the chosen columns (all columns: the sample count)."""
+    return int(_need("vcfc_extract_workspace_size")(n_records, n_cols))
+
+
+def extract_samples_device(d_in, in_bytes, d_rec_start, d_select, n, samples, cols, d_out, out_cap, d_rec_off, d_ws,
+                           ws_bytes, d_err, stream=0):
+    """Device-resident records cut to the sample columns `cols` (host list;
+    None: all) and written as .vcfc records at d_out + d_rec_off[i]
+    (include/vcfc.h vcfc_extract_samples_device); d_select may be None.
+    Returns the status (VCFC_E_ARG for bad columns); enqueued on `stream`."""
+    c = None if cols is None else np.asarray(cols, dtype=np.uint32)
+    cp, k = (None, 0) if c is None else (c.ctypes.data, len(c))
+    if c is not None and k == 0:
+        cp = np.zeros(1, dtype=np.uint32).ctypes.data
+    return _need("vcfc_extract_samples_device")(d_in, in_bytes, d_rec_start, d_select, n, samples, cp, k, d_out, out_cap,
+                                                d_rec_off, d_ws, ws_bytes, d_err, stream)
 
 
 def counts_workspace_size(n_records, samples):
