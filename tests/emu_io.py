@@ -7,8 +7,38 @@ import subprocess
 import numpy as np
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_SO = os.path.join(REPO, "tests", "simt_emu", "_build", "libvcfc_emu.so")
+EMU_DIR = os.path.join(REPO, "tests", "simt_emu")
+CSRC = os.path.join(REPO, "vcf-compression_amd", "csrc")
+EMU_SO = os.path.join(EMU_DIR, "_build", "libvcfc_emu.so")
 _lib = None
+
+
+def build_emu_lib(name, hip_sources, api_cpp):
+    """_build/libvcfc_<name>_emu.so: the csrc kernels `hip_sources` and the
+    entry points `api_cpp` against the emulator (flags as
+    tests/simt_emu/Makefile), loaded.  It is rebuilt when any csrc header,
+    any file of tests/simt_emu or a source is newer: the directories are
+    listed, so no header can be missing from the list."""
+    import fcntl
+    so = os.path.join(EMU_DIR, "_build", "libvcfc_%s_emu.so" % name)
+    os.makedirs(os.path.dirname(so), exist_ok=True)
+    srcs = [os.path.join(CSRC, f) for f in hip_sources]
+    deps = srcs + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    for d, sub, files in os.walk(EMU_DIR):
+        sub[:] = [x for x in sub if x != "_build"]
+        deps += [os.path.join(d, f) for f in files]
+    with open(so + ".lock", "w") as lk:   # one build at a time (pytest -n workers)
+        fcntl.flock(lk, fcntl.LOCK_EX)
+        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
+            cmd = ["g++", "-std=c++17", "-O2", "-g", "-fPIC", "-shared", '-DVCFC_DIAG="diag_retries.h"', "-Wall",
+                   "-Wno-unused-function", "-Wno-unknown-pragmas", "-Wno-attributes", "-I" + EMU_DIR, "-I" + CSRC]
+            for s in srcs:
+                cmd += ["-x", "c++", s]
+            cmd += ["-x", "none", os.path.join(EMU_DIR, "emu.cpp"), os.path.join(EMU_DIR, api_cpp), "-pthread", "-o",
+                    so + ".tmp"]
+            subprocess.run(cmd, check=True)
+            os.replace(so + ".tmp", so)
+    return ctypes.CDLL(so)
 
 
 def lib():

@@ -9,6 +9,7 @@
 #include "vcfc_device.h"
 #include "vcfc_decode_driver.h"
 #include "emu.h"
+#include "host_buffers.h"
 #include <atomic>
 
 // bytes the hop line index's walkers loaded (VCFC_DIAG_HOP_READ, diag_retries.h)
@@ -74,16 +75,6 @@ extern "C" int emu_sparse_plan(const uint8_t *recs, const uint64_t *rec_off, uin
 // The product decode driver (csrc/vcfc_decode_driver.h) over host memory:
 // header parse + decode_section with small output batches (exercises the
 // batching).  Returns the driver status; *out_len = bytes produced.
-namespace {
-struct HostBuffers : vcfc_dec::Buffers {
-    std::vector<uint8_t> b[N_SLOTS];
-    void *get(int slot, uint64_t bytes) override {
-        if (b[slot].size() < bytes) b[slot].assign(bytes, 0xCD);   // poison
-        return b[slot].data();
-    }
-};
-}  // namespace
-
 extern "C" int emu_decompress(const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len,
                               uint64_t out_batch) {
     uint64_t data_off = 0, S = 0;

@@ -11,16 +11,7 @@
 #include "vcfc_device.h"
 #include "vcfc_counts_driver.h"
 #include "emu.h"
-
-namespace {
-struct HostBuffers : vcfc_dec::Buffers {
-    std::vector<uint8_t> b[N_SLOTS];
-    void *get(int slot, uint64_t bytes) override {
-        if (b[slot].size() < bytes) b[slot].assign(bytes, 0xCD);   // poison
-        return b[slot].data();
-    }
-};
-}  // namespace
+#include "host_buffers.h"
 
 extern "C" uint64_t emu_counts_lds_samples() { return VCFC_COUNTS_LDS_SAMPLES; }
 extern "C" uint64_t emu_counts_workspace_size(uint64_t n, uint64_t S) { return vcfc_counts_workspace_layout(n, S).total; }

@@ -11,21 +11,15 @@
 #include "vcfc_extract_driver.h"
 #include "vcfc_regions_driver.h"
 #include "emu.h"
-
-namespace {
-struct HostBuffers : vcfc_dec::Buffers {
-    std::vector<uint64_t> b[N_SLOTS];   // 8-byte aligned, as device allocations are
-    void *get(int slot, uint64_t bytes) override {
-        if (b[slot].size() * 8 < bytes) b[slot].assign(bytes / 8 + 1, 0xCDCDCDCDCDCDCDCDull);   // poison
-        return b[slot].data();
-    }
-};
-}  // namespace
+#include "host_buffers.h"
 
 extern "C" uint64_t emu_extract_bound(uint64_t in_bytes, uint64_t n_records, uint64_t K) {
     return vcfc_ext::extract_bound(in_bytes, n_records, K);
 }
 extern "C" uint64_t emu_extract_tile(void) { return VCFC_EXTRACT_TILE; }
+
+static uint64_t g_sink_calls = 0;   // pieces the last emu_extract sank (header included)
+extern "C" uint64_t emu_extract_sink_calls() { return g_sink_calls; }
 
 extern "C" int emu_regions_build(const char *text, uint64_t len, uint8_t *table, uint64_t cap, uint64_t *bytes,
                                  uint64_t *n_regions, uint64_t *bad_line) {
@@ -44,7 +38,9 @@ extern "C" int emu_extract(const uint8_t *in, uint64_t n, const uint32_t *cols, 
     int st = c.prepare(in, n, cols, K);
     if (st) return st;
     uint64_t o = 0;
+    g_sink_calls = 0;
     auto sink = [&](const uint8_t *p, uint64_t k) {
+        g_sink_calls++;
         if (o + k > cap) return false;
         memcpy(out + o, p, k);
         o += k;
@@ -70,18 +66,9 @@ extern "C" int emu_extract_device(const uint8_t *recs, const uint64_t *rec, cons
                                   uint64_t *err) {
     std::vector<uint32_t> csort, rank;
     if (vcfc_ext::device_columns(cols, K, S, csort, rank)) return vcfc_ext::ST_E_ARG;
-    K = csort.size();
-    const VcfcSubsetLayout L = vcfc_extract_workspace_layout(n, K);
-    std::vector<uint8_t> ws(L.total + 64, 0xCD);
+    std::vector<uint8_t> ws(vcfc_extract_workspace_layout(n, csort.size()).total + 64, 0xCD);
     std::vector<uint8_t> in(recs, recs + (n ? rec[n] : 0));
     in.resize(in.size() + 64, 0xCD);
-    VcfcExtractArgs a;
-    a.in = in.data(); a.n_bytes = n ? rec[n] : 0; a.rec_start = rec; a.select = select; a.n = n; a.S = S;
-    a.K = (uint32_t)K; a.out = out; a.out_cap = out_cap; a.line_off = rec_off;
-    vcfc_subset_args_workspace(a, ws.data(), L);
-    a.err = err;
-    memcpy(ws.data() + L.csort, csort.data(), 4 * K);
-    memcpy(ws.data() + L.rank, rank.data(), 4 * K);
-    if (vcfc_extract_plan(a, nullptr) != hipSuccess) return vcfc_ext::ST_E_HIP;
-    return vcfc_extract_write(a, 0, n, nullptr) == hipSuccess ? 0 : vcfc_ext::ST_E_HIP;
+    return vcfc_sub::records_device(vcfc_ext::EXTRACT, in.data(), n ? rec[n] : 0, rec, select, n, S, csort, rank, out, out_cap,
+                                    rec_off, ws.data(), ws.size(), err, nullptr);
 }

@@ -13,16 +13,9 @@
 #include "vcfc_device.h"
 #include "vcfc_index_driver.h"
 #include "emu.h"
+#include "host_buffers.h"
 
 namespace {
-struct HostBuffers : vcfc_dec::Buffers {
-    std::vector<uint8_t> b[N_SLOTS];
-    void *get(int slot, uint64_t bytes) override {
-        if (b[slot].size() < bytes) b[slot].assign(bytes, 0xCD);   // poison
-        return b[slot].data();
-    }
-};
-
 // A copy of [p, p + n) that ends at a page with no access: a read past the
 // last record's end faults.
 struct Guarded {

@@ -12,16 +12,7 @@
 #include "vcfc_matrix_driver.h"
 #include "vcfc_regions_driver.h"
 #include "emu.h"
-
-namespace {
-struct HostBuffers : vcfc_dec::Buffers {
-    std::vector<uint64_t> b[N_SLOTS];   // 8-byte aligned, as device allocations are
-    void *get(int slot, uint64_t bytes) override {
-        if (b[slot].size() * 8 < bytes) b[slot].assign(bytes / 8 + 1, 0xCDCDCDCDCDCDCDCDull);   // poison
-        return b[slot].data();
-    }
-};
-}  // namespace
+#include "host_buffers.h"
 
 extern "C" uint64_t emu_matrix_row_bytes(int layout, uint64_t S) { return vcfc_matrix_row_size(layout, S); }
 extern "C" uint64_t emu_matrix_lds_samples(int layout) { return vcfc_matrix_tile_samples(layout); }

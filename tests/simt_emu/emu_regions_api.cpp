@@ -13,16 +13,9 @@
 #include "vcfc_regions_driver.h"
 #include "vcfc_subset_driver.h"
 #include "emu.h"
+#include "host_buffers.h"
 
 namespace {
-struct HostBuffers : vcfc_dec::Buffers {
-    std::vector<uint64_t> b[N_SLOTS];   // 8-byte aligned, as device allocations are
-    void *get(int slot, uint64_t bytes) override {
-        if (b[slot].size() * 8 < bytes) b[slot].assign(bytes / 8 + 1, 0xCDCDCDCDCDCDCDCDull);   // poison
-        return b[slot].data();
-    }
-};
-
 struct OutSink {
     uint8_t *out;
     uint64_t cap, o = 0;
@@ -89,16 +82,13 @@ extern "C" int emu_regions_query_samples(const uint8_t *in, uint64_t n, const ui
                                          uint64_t out_batch) {
     *out_len = 0;
     if (!vcfc_reg::regions_validate(table, table_bytes)) return vcfc_reg::ST_E_ARG;
-    std::vector<uint8_t> hdr;
-    std::vector<uint32_t> csort, rank;
-    uint64_t data_off = 0, S = 0;
-    int st = vcfc_sub::subset_header(in, n, cols, K, hdr, &data_off, &S);
-    if (!st) st = vcfc_sub::sort_columns(cols, K, S, csort, rank);
+    vcfc_sub::Call c;
+    int st = c.prepare(in, n, cols, K);
     if (st) return st;
     OutSink sink{out, cap};
     const uint8_t *d_table = nullptr;
     HostBuffers B;
-    st = vcfc_sub::matched_section(in + data_off, n - data_off, S, csort, rank,
+    st = vcfc_sub::matched_section(in + c.data_off, n - c.data_off, c.S, c.csort, c.rank,
                                    vcfc_reg::regions_step(table, table_bytes, &d_table), B, nullptr, std::ref(sink), out_batch);
     *out_len = sink.o;
     return st;

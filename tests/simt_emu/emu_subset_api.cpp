@@ -10,27 +10,12 @@
 #include "vcfc_device.h"
 #include "vcfc_subset_driver.h"
 #include "emu.h"
+#include "host_buffers.h"
 
-namespace {
-struct HostBuffers : vcfc_dec::Buffers {
-    std::vector<uint8_t> b[N_SLOTS];
-    void *get(int slot, uint64_t bytes) override {
-        if (b[slot].size() < bytes) b[slot].assign(bytes, 0xCD);   // poison
-        return b[slot].data();
-    }
-};
+using vcfc_sub::Call;
 
-struct Call {
-    std::vector<uint8_t> hdr;
-    std::vector<uint32_t> csort, rank;
-    uint64_t data_off = 0, S = 0;
-    int prepare(const uint8_t *in, uint64_t n, const uint32_t *cols, uint64_t K) {
-        int st = vcfc_sub::subset_header(in, n, cols, K, hdr, &data_off, &S);
-        if (!st) st = vcfc_sub::sort_columns(cols, K, S, csort, rank);
-        return st;
-    }
-};
-}  // namespace
+static uint64_t g_sink_calls = 0;   // pieces the last emu_subset_decompress sank (header included)
+extern "C" uint64_t emu_subset_sink_calls() { return g_sink_calls; }
 
 // decompress-samples over a whole .vcfc (the C ABI's control flow)
 extern "C" int emu_subset_decompress(const uint8_t *in, uint64_t n, const uint32_t *cols, uint64_t K, uint8_t *out,
@@ -40,7 +25,9 @@ extern "C" int emu_subset_decompress(const uint8_t *in, uint64_t n, const uint32
     int st = c.prepare(in, n, cols, K);
     if (st) return st;
     uint64_t o = 0;
+    g_sink_calls = 0;
     auto sink = [&](const uint8_t *p, uint64_t k) {
+        g_sink_calls++;
         if (o + k > cap) return false;
         memcpy(out + o, p, k);
         o += k;
@@ -82,19 +69,11 @@ extern "C" int emu_subset_device(const uint8_t *recs, const uint64_t *rec, const
                                  uint64_t *err) {
     std::vector<uint32_t> csort, rank;
     if (vcfc_sub::sort_columns(cols, K, S, csort, rank)) return vcfc_sub::ST_E_ARG;
-    const VcfcSubsetLayout L = vcfc_subset_workspace_layout(n, K);
-    std::vector<uint8_t> ws(L.total + 64, 0xCD);
+    std::vector<uint8_t> ws(vcfc_subset_workspace_layout(n, K).total + 64, 0xCD);
     std::vector<uint8_t> in(recs, recs + (n ? rec[n] : 0));
     in.resize(in.size() + 64, 0xCD);
-    VcfcSubsetArgs a;
-    a.in = in.data(); a.n_bytes = n ? rec[n] : 0; a.rec_start = rec; a.select = select; a.n = n; a.S = S;
-    a.K = (uint32_t)K; a.out = out; a.out_cap = out_cap; a.line_off = line_off;
-    vcfc_subset_args_workspace(a, ws.data(), L);
-    a.err = err;
-    memcpy(ws.data() + L.csort, csort.data(), 4 * K);
-    memcpy(ws.data() + L.rank, rank.data(), 4 * K);
-    if (vcfc_subset_plan(a, nullptr) != hipSuccess) return vcfc_sub::ST_E_HIP;
-    return vcfc_subset_write(a, 0, n, nullptr) == hipSuccess ? 0 : vcfc_sub::ST_E_HIP;
+    return vcfc_sub::records_device(vcfc_sub::SUBSET, in.data(), n ? rec[n] : 0, rec, select, n, S, csort, rank, out, out_cap,
+                                    line_off, ws.data(), ws.size(), err, nullptr);
 }
 
 extern "C" int emu_sample_columns(const uint8_t *in, uint64_t n, const char *names, uint64_t names_len, uint32_t *cols,

@@ -7,22 +7,16 @@ product kernels (csrc/vcfc_extract.hip) and host driver
 the restatement: whole bytes, status, error word and offsets.
 test_gpu_extract.py repeats it on the GPU."""
 import ctypes
-import fcntl
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import decode_cases as D
+import emu_io as E
 import extract_cases as EC
 import golden_io as G
 import subset_cases as SC
 
-REPO = G.REPO
-EMU_DIR = os.path.join(REPO, "tests", "simt_emu")
-CSRC = os.path.join(REPO, "vcf-compression_amd", "csrc")
-SO = os.path.join(EMU_DIR, "_build", "libvcfc_extract_emu.so")
 OK, E_NOSPACE, E_ARG, E_FORMAT = EC.OK, EC.E_NOSPACE, EC.E_ARG, EC.E_FORMAT
 _lib = None
 
@@ -32,24 +26,8 @@ def lib():
     global _lib
     if _lib is not None:
         return _lib
-    os.makedirs(os.path.dirname(SO), exist_ok=True)
-    srcs = [os.path.join(CSRC, f) for f in ("vcfc_extract.hip", "vcfc_regions.hip", "vcfc_decode.hip", "vcfc_encode.hip")]
-    deps = srcs + [os.path.join(CSRC, f) for f in ("vcfc_extract_driver.h", "vcfc_subset_driver.h", "vcfc_regions_driver.h",
-                                                   "vcfc_decode_driver.h", "vcfc_decode_dev.h", "vcfc_query_dev.h",
-                                                   "vcfc_device.h")] + \
-        [os.path.join(EMU_DIR, f) for f in ("emu.cpp", "emu.h", "emu_extract_api.cpp", "vcfc_wave.h", "hip/hip_runtime.h")]
-    with open(SO + ".lock", "w") as lk:
-        fcntl.flock(lk, fcntl.LOCK_EX)
-        if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
-            cmd = ["g++", "-std=c++17", "-O2", "-g", "-fPIC", "-shared", '-DVCFC_DIAG="diag_retries.h"', "-Wall",
-                   "-Wno-unused-function", "-Wno-unknown-pragmas", "-Wno-attributes", "-I" + EMU_DIR, "-I" + CSRC]
-            for s in srcs:
-                cmd += ["-x", "c++", s]
-            cmd += ["-x", "none", os.path.join(EMU_DIR, "emu.cpp"), os.path.join(EMU_DIR, "emu_extract_api.cpp"),
-                    "-pthread", "-o", SO + ".tmp"]
-            subprocess.run(cmd, check=True)
-            os.replace(SO + ".tmp", SO)
-    L = ctypes.CDLL(SO)
+    L = E.build_emu_lib("extract", ("vcfc_extract.hip", "vcfc_regions.hip", "vcfc_decode.hip", "vcfc_encode.hip"),
+                        "emu_extract_api.cpp")
     vp, u64, cp, ci = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_int
     pu64 = ctypes.POINTER(u64)
     L.emu_extract_bound.restype = u64
@@ -190,6 +168,21 @@ def test_batch_sizes():
     for name, data in SC.batch_files():   # one output batch per record, and one for all
         for ob in (1, 1 << 30):
             assert emu_ext(data, [69, 0, 33], out_batch=ob) == EC.extract(data, [69, 0, 33]), (name, ob)
+
+
+def test_batch_boundary():
+    """A batch takes records while their total is at most out_batch (the
+    output's bytes do not show it, the pieces sunk do): two records, out_batch
+    their total, are one piece behind the header; one byte less, two."""
+    data = D.valid_files(1)[2][1]   # S = 64
+    h = SC.parse_header(data)[0]
+    two = data[:h + SC.hop(data[h:])[0][2]]
+    st, want = EC.extract(two, [5, 2])
+    body = len(want) - SC.parse_header(want)[0]
+    assert st == OK and len(SC.hop(want[len(want) - body:])[0]) == 2
+    for ob, pieces in ((body, 2), (body - 1, 3)):
+        assert emu_ext(two, [5, 2], out_batch=ob) == (st, want)
+        assert lib().emu_extract_sink_calls() == pieces, ob
 
 
 def test_query_files_and_region_tables():

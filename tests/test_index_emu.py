@@ -5,21 +5,15 @@ against the reference CLI's recorded results
 against the fiber SIMT emulator, against the goldens and the restatement.
 test_gpu_index.py repeats the valid-input part on the GPU."""
 import ctypes
-import fcntl
-import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
+import emu_io
 import golden_io as G
 import index_cases as X
 
-REPO = G.REPO
-EMU_DIR = os.path.join(REPO, "tests", "simt_emu")
-CSRC = os.path.join(REPO, "vcf-compression_amd", "csrc")
-SO = os.path.join(EMU_DIR, "_build", "libvcfc_index_emu.so")
 OK, E_ARG, E_FORMAT = 0, 5, 8
 NO_ERROR = (1 << 64) - 1
 _lib = None
@@ -30,23 +24,7 @@ def lib():
     global _lib
     if _lib is not None:
         return _lib
-    os.makedirs(os.path.dirname(SO), exist_ok=True)
-    srcs = [os.path.join(CSRC, f) for f in ("vcfc_index.hip", "vcfc_decode.hip", "vcfc_encode.hip")]
-    deps = srcs + [os.path.join(CSRC, f) for f in ("vcfc_index_driver.h", "vcfc_decode_driver.h", "vcfc_decode_dev.h",
-                                                   "vcfc_device.h")] + \
-        [os.path.join(EMU_DIR, f) for f in ("emu.cpp", "emu.h", "emu_index_api.cpp", "vcfc_wave.h", "hip/hip_runtime.h")]
-    with open(SO + ".lock", "w") as lk:
-        fcntl.flock(lk, fcntl.LOCK_EX)
-        if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
-            cmd = ["g++", "-std=c++17", "-O2", "-g", "-fPIC", "-shared", '-DVCFC_DIAG="diag_retries.h"', "-Wall",
-                   "-Wno-unused-function", "-Wno-unknown-pragmas", "-Wno-attributes", "-I" + EMU_DIR, "-I" + CSRC]
-            for s in srcs:
-                cmd += ["-x", "c++", s]
-            cmd += ["-x", "none", os.path.join(EMU_DIR, "emu.cpp"), os.path.join(EMU_DIR, "emu_index_api.cpp"),
-                    "-pthread", "-o", SO + ".tmp"]
-            subprocess.run(cmd, check=True)
-            os.replace(SO + ".tmp", SO)
-    L = ctypes.CDLL(SO)
+    L = emu_io.build_emu_lib("index", ("vcfc_index.hip", "vcfc_decode.hip", "vcfc_encode.hip"), "emu_index_api.cpp")
     vp, u64, cp = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_char_p
     pu64 = ctypes.POINTER(u64)
     L.emu_index_create.argtypes = [cp, u64, u64, vp, u64, pu64, ctypes.POINTER(ctypes.c_int64)]

@@ -7,23 +7,17 @@ emulator, held to the restatement: status, failing record, indices, rows and
 the three export-bed files, all exact, and every byte of the output
 allocation outside the rows.  test_gpu_matrix.py repeats it on the GPU."""
 import ctypes
-import fcntl
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import counts_cases as CC
 import decode_cases as D
+import emu_io as E
 import golden_io as G
 import matrix_cases as MC
 import subset_cases as SC
 
-REPO = G.REPO
-EMU_DIR = os.path.join(REPO, "tests", "simt_emu")
-CSRC = os.path.join(REPO, "vcf-compression_amd", "csrc")
-SO = os.path.join(EMU_DIR, "_build", "libvcfc_matrix_emu.so")
 OK, E_ARG, E_FORMAT = MC.OK, MC.E_ARG, MC.E_FORMAT
 _lib = None
 
@@ -33,24 +27,8 @@ def lib():
     global _lib
     if _lib is not None:
         return _lib
-    os.makedirs(os.path.dirname(SO), exist_ok=True)
-    srcs = [os.path.join(CSRC, f) for f in ("vcfc_matrix.hip", "vcfc_regions.hip", "vcfc_decode.hip", "vcfc_encode.hip")]
-    deps = srcs + [os.path.join(CSRC, f) for f in ("vcfc_matrix_driver.h", "vcfc_counts_driver.h", "vcfc_regions_driver.h",
-                                                   "vcfc_subset_driver.h", "vcfc_decode_driver.h", "vcfc_decode_dev.h",
-                                                   "vcfc_query_dev.h", "vcfc_device.h")] + \
-        [os.path.join(EMU_DIR, f) for f in ("emu.cpp", "emu.h", "emu_matrix_api.cpp", "vcfc_wave.h", "hip/hip_runtime.h")]
-    with open(SO + ".lock", "w") as lk:
-        fcntl.flock(lk, fcntl.LOCK_EX)
-        if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
-            cmd = ["g++", "-std=c++17", "-O2", "-g", "-fPIC", "-shared", '-DVCFC_DIAG="diag_retries.h"', "-Wall",
-                   "-Wno-unused-function", "-Wno-unknown-pragmas", "-Wno-attributes", "-I" + EMU_DIR, "-I" + CSRC]
-            for s in srcs:
-                cmd += ["-x", "c++", s]
-            cmd += ["-x", "none", os.path.join(EMU_DIR, "emu.cpp"), os.path.join(EMU_DIR, "emu_matrix_api.cpp"),
-                    "-pthread", "-o", SO + ".tmp"]
-            subprocess.run(cmd, check=True)
-            os.replace(SO + ".tmp", SO)
-    L = ctypes.CDLL(SO)
+    L = E.build_emu_lib("matrix", ("vcfc_matrix.hip", "vcfc_regions.hip", "vcfc_decode.hip", "vcfc_encode.hip"),
+                        "emu_matrix_api.cpp")
     vp, u64, cp, ci = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_int
     pu64 = ctypes.POINTER(u64)
     L.emu_matrix_row_bytes.restype = L.emu_matrix_lds_samples.restype = L.emu_matrix_workspace_size.restype = u64

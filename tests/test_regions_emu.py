@@ -7,22 +7,16 @@ fiber SIMT emulator, held to the restatement: table bytes, flags, error word,
 status and output bytes, all exact.  test_gpu_regions.py repeats it on the
 GPU."""
 import ctypes
-import fcntl
 import hashlib
-import os
 import struct
-import subprocess
 
 import numpy as np
 
+import emu_io as E
 import golden_io as G
 import regions_cases as RC
 import subset_cases as SC
 
-REPO = G.REPO
-EMU_DIR = os.path.join(REPO, "tests", "simt_emu")
-CSRC = os.path.join(REPO, "vcf-compression_amd", "csrc")
-SO = os.path.join(EMU_DIR, "_build", "libvcfc_regions_emu.so")
 OK, E_NOSPACE, E_ARG, E_FORMAT = RC.OK, RC.E_NOSPACE, RC.E_ARG, RC.E_FORMAT
 _lib = None
 
@@ -32,25 +26,8 @@ def lib():
     global _lib
     if _lib is not None:
         return _lib
-    os.makedirs(os.path.dirname(SO), exist_ok=True)
-    srcs = [os.path.join(CSRC, f) for f in ("vcfc_regions.hip", "vcfc_decode.hip", "vcfc_subset.hip", "vcfc_counts.hip",
-                                            "vcfc_encode.hip")]
-    deps = srcs + [os.path.join(CSRC, f) for f in ("vcfc_regions_driver.h", "vcfc_counts_driver.h", "vcfc_subset_driver.h",
-                                                   "vcfc_decode_driver.h", "vcfc_decode_dev.h", "vcfc_query_dev.h",
-                                                   "vcfc_device.h")] + \
-        [os.path.join(EMU_DIR, f) for f in ("emu.cpp", "emu.h", "emu_regions_api.cpp", "vcfc_wave.h", "hip/hip_runtime.h")]
-    with open(SO + ".lock", "w") as lk:
-        fcntl.flock(lk, fcntl.LOCK_EX)
-        if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
-            cmd = ["g++", "-std=c++17", "-O2", "-g", "-fPIC", "-shared", '-DVCFC_DIAG="diag_retries.h"', "-Wall",
-                   "-Wno-unused-function", "-Wno-unknown-pragmas", "-Wno-attributes", "-I" + EMU_DIR, "-I" + CSRC]
-            for s in srcs:
-                cmd += ["-x", "c++", s]
-            cmd += ["-x", "none", os.path.join(EMU_DIR, "emu.cpp"), os.path.join(EMU_DIR, "emu_regions_api.cpp"),
-                    "-pthread", "-o", SO + ".tmp"]
-            subprocess.run(cmd, check=True)
-            os.replace(SO + ".tmp", SO)
-    L = ctypes.CDLL(SO)
+    L = E.build_emu_lib("regions", ("vcfc_regions.hip", "vcfc_decode.hip", "vcfc_subset.hip", "vcfc_counts.hip",
+                        "vcfc_encode.hip"), "emu_regions_api.cpp")
     vp, u64, cp, ci = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_int
     pu64 = ctypes.POINTER(u64)
     L.emu_regions_build.argtypes = [cp, u64, vp, u64, pu64, pu64, pu64]

@@ -5,21 +5,15 @@ kernels (csrc/vcfc_subset.hip) and host driver (csrc/vcfc_subset_driver.h)
 compiled against the fiber SIMT emulator, held to the restatement: whole
 bytes and status.  test_gpu_subset.py repeats it on the GPU."""
 import ctypes
-import fcntl
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import decode_cases as D
+import emu_io as E
 import golden_io as G
 import subset_cases as SC
 
-REPO = G.REPO
-EMU_DIR = os.path.join(REPO, "tests", "simt_emu")
-CSRC = os.path.join(REPO, "vcf-compression_amd", "csrc")
-SO = os.path.join(EMU_DIR, "_build", "libvcfc_subset_emu.so")
 OK, E_ARG, E_FORMAT = SC.OK, SC.E_ARG, SC.E_FORMAT
 NO_ERROR = (1 << 64) - 1
 _lib = None
@@ -30,23 +24,7 @@ def lib():
     global _lib
     if _lib is not None:
         return _lib
-    os.makedirs(os.path.dirname(SO), exist_ok=True)
-    srcs = [os.path.join(CSRC, f) for f in ("vcfc_subset.hip", "vcfc_decode.hip", "vcfc_encode.hip")]
-    deps = srcs + [os.path.join(CSRC, f) for f in ("vcfc_subset_driver.h", "vcfc_decode_driver.h", "vcfc_decode_dev.h",
-                                                   "vcfc_device.h")] + \
-        [os.path.join(EMU_DIR, f) for f in ("emu.cpp", "emu.h", "emu_subset_api.cpp", "vcfc_wave.h", "hip/hip_runtime.h")]
-    with open(SO + ".lock", "w") as lk:
-        fcntl.flock(lk, fcntl.LOCK_EX)
-        if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
-            cmd = ["g++", "-std=c++17", "-O2", "-g", "-fPIC", "-shared", '-DVCFC_DIAG="diag_retries.h"', "-Wall",
-                   "-Wno-unused-function", "-Wno-unknown-pragmas", "-Wno-attributes", "-I" + EMU_DIR, "-I" + CSRC]
-            for s in srcs:
-                cmd += ["-x", "c++", s]
-            cmd += ["-x", "none", os.path.join(EMU_DIR, "emu.cpp"), os.path.join(EMU_DIR, "emu_subset_api.cpp"),
-                    "-pthread", "-o", SO + ".tmp"]
-            subprocess.run(cmd, check=True)
-            os.replace(SO + ".tmp", SO)
-    L = ctypes.CDLL(SO)
+    L = E.build_emu_lib("subset", ("vcfc_subset.hip", "vcfc_decode.hip", "vcfc_encode.hip"), "emu_subset_api.cpp")
     vp, u64, cp = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_char_p
     pu64 = ctypes.POINTER(u64)
     L.emu_subset_decompress.argtypes = [cp, u64, vp, u64, vp, u64, pu64, u64]
@@ -169,6 +147,21 @@ def test_batch_sizes():
     for name, data in SC.batch_files():   # one output batch per line, and one for all
         for ob in (1, 1 << 30):
             assert emu_dec(data, [69, 0, 33], out_batch=ob) == SC.subset(data, [69, 0, 33]), (name, ob)
+
+
+def test_batch_boundary():
+    """A batch takes lines while their total is at most out_batch (the output's
+    bytes do not show it, the pieces sunk do): two lines, out_batch their
+    total, are one piece behind the header; one byte less, two."""
+    data = D.valid_files(1)[2][1]   # S = 64
+    h = SC.parse_header(data)[0]
+    two = data[:h + SC.hop(data[h:])[0][2]]
+    st, want = SC.subset(two, [5, 2])
+    lines = want[want.index(b"\n#CHROM"):].split(b"\n", 2)[2]
+    assert st == OK and lines.count(b"\n") == 2
+    for ob, pieces in ((len(lines), 2), (len(lines) - 1, 3)):
+        assert emu_dec(two, [5, 2], out_batch=ob) == (st, want)
+        assert lib().emu_subset_sink_calls() == pieces, ob
 
 
 @pytest.mark.parametrize("seed", [1])

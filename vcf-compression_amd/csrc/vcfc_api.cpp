@@ -159,6 +159,43 @@ int write_all_at(int fd, const void *p, uint64_t len, uint64_t off) {
     return VCFC_OK;
 }
 
+// The sinks (vcfc_dec::Sink) of the calls that decode.  A buffer call's: counts
+// every byte, copies while they fit (pass std::ref; VCFC_E_NOSPACE if !fits).
+struct BufferSink {
+    uint8_t *out;
+    uint64_t cap, o = 0;
+    bool fits = true;
+    bool operator()(const uint8_t *p, uint64_t k) {
+        if (fits && o + k <= cap) memcpy(out + o, p, k);
+        else fits = false;
+        o += k;
+        return true;
+    }
+};
+// of a call that writes to a descriptor the caller opened
+struct FdSink {
+    int fd;
+    bool operator()(const uint8_t *p, uint64_t k) const {
+        while (k) {
+            const ssize_t w = write(fd, p, std::min<uint64_t>(k, 1ull << 30));
+            if (w <= 0) return false;
+            p += w;
+            k -= (uint64_t)w;
+        }
+        return true;
+    }
+};
+// of a call that writes a file of its own, at offsets from 0
+struct FileSink {
+    int fd;
+    uint64_t o = 0;
+    bool operator()(const uint8_t *p, uint64_t k) {
+        if (write_all_at(fd, p, k, o)) return false;
+        o += k;
+        return true;
+    }
+};
+
 void put_be64(uint8_t *o, uint64_t v) {
     for (int k = 0; k < 8; k++) o[k] = (uint8_t)(v >> (56 - 8 * k));
 }
@@ -840,20 +877,12 @@ int vcfc_decompress_buffer(vcfc_ctx *c, const uint8_t *in, uint64_t n, uint8_t *
     uint64_t data_off = 0, S = 0;
     int st = parse_vcfc_header(in, n, &data_off, &S);
     if (st) return st;   // the reference writes nothing before its header check passes
-    uint64_t o = 0;
-    bool fits = true;
-    auto sink = [&](const uint8_t *p, uint64_t k) {
-        if (fits && o + k <= out_cap) memcpy(out + o, p, k);
-        else fits = false;
-        o += k;
-        return true;
-    };
-    sink(in, data_off);
+    BufferSink bs{out, out_cap};
+    bs(in, data_off);
     CtxDecodeBuffers B(c);
-    st = vcfc_dec::decode_section(in + data_off, n - data_off, S, B, c->stream, sink);
-    *out_len = o;
-    if (!fits) return VCFC_E_NOSPACE;
-    return st;
+    st = vcfc_dec::decode_section(in + data_off, n - data_off, S, B, c->stream, std::ref(bs));
+    *out_len = bs.o;
+    return bs.fits ? st : VCFC_E_NOSPACE;
 }
 
 int vcfc_decompress_file(vcfc_ctx *c, const char *in_path, const char *out_path) {
@@ -867,16 +896,11 @@ int vcfc_decompress_file(vcfc_ctx *c, const char *in_path, const char *out_path)
     if (fd < 0) return VCFC_E_IO;
     uint64_t data_off = 0, S = 0;
     st = parse_vcfc_header(f.p, f.n, &data_off, &S);
-    uint64_t o = 0;
-    auto sink = [&](const uint8_t *p, uint64_t k) {
-        if (write_all_at(fd, p, k, o)) return false;
-        o += k;
-        return true;
-    };
-    if (!st && !sink(f.p, data_off)) st = VCFC_E_IO;
+    FileSink fs{fd};
+    if (!st && !fs(f.p, data_off)) st = VCFC_E_IO;
     if (!st) {
         CtxDecodeBuffers B(c);
-        st = vcfc_dec::decode_section(f.p + data_off, f.n - data_off, S, B, c->stream, sink);
+        st = vcfc_dec::decode_section(f.p + data_off, f.n - data_off, S, B, c->stream, std::ref(fs));
     }
     close(fd);
     return st;
@@ -901,20 +925,12 @@ int vcfc_query_buffer(vcfc_ctx *c, const uint8_t *in, uint64_t n, const char *re
     uint64_t data_off = 0, S = 0;
     int st = parse_vcfc_header(in, n, &data_off, &S);
     if (st) return st;
-    uint64_t o = 0;
-    bool fits = true;
-    auto sink = [&](const uint8_t *p, uint64_t k) {
-        if (fits && o + k <= out_cap) memcpy(out + o, p, k);
-        else fits = false;
-        o += k;
-        return true;
-    };
+    BufferSink bs{out, out_cap};
     CtxDecodeBuffers B(c);
     st = vcfc_dec::query_section(in + data_off, n - data_off, S, reinterpret_cast<const uint8_t *>(ref), ref_len,
-                                 has_range, start, end, B, c->stream, sink);
-    *out_len = o;
-    if (!fits) return VCFC_E_NOSPACE;
-    return st;
+                                 has_range, start, end, B, c->stream, std::ref(bs));
+    *out_len = bs.o;
+    return bs.fits ? st : VCFC_E_NOSPACE;
 }
 
 int vcfc_query_file(vcfc_ctx *c, const char *in_path, const char *ref, uint64_t ref_len, int has_range,
@@ -926,18 +942,9 @@ int vcfc_query_file(vcfc_ctx *c, const char *in_path, const char *ref, uint64_t 
     if (st) return st;
     uint64_t data_off = 0, S = 0;
     if ((st = parse_vcfc_header(f.p, f.n, &data_off, &S))) return st;
-    auto sink = [&](const uint8_t *p, uint64_t k) {
-        while (k) {
-            const ssize_t w = write(out_fd, p, std::min<uint64_t>(k, 1ull << 30));
-            if (w <= 0) return false;
-            p += w;
-            k -= (uint64_t)w;
-        }
-        return true;
-    };
     CtxDecodeBuffers B(c);
     return vcfc_dec::query_section(f.p + data_off, f.n - data_off, S, reinterpret_cast<const uint8_t *>(ref), ref_len,
-                                   has_range, start, end, B, c->stream, sink);
+                                   has_range, start, end, B, c->stream, FdSink{out_fd});
 }
 
 // ---- sparse-file query: query_sparse_file_fd, reference
@@ -948,20 +955,11 @@ int vcfc_sparse_query_file(vcfc_ctx *c, const char *in_path, const char *ref, ui
     if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
     const int fd = open(in_path, O_RDONLY);
     if (fd < 0) return VCFC_E_IO;
-    auto sink = [&](const uint8_t *p, uint64_t k) {
-        while (k) {
-            const ssize_t w = write(out_fd, p, std::min<uint64_t>(k, 1ull << 30));
-            if (w <= 0) return false;
-            p += w;
-            k -= (uint64_t)w;
-        }
-        return true;
-    };
     vcfc_dec::SparseQuery q;
     q.ref = reinterpret_cast<const uint8_t *>(ref); q.ref_len = ref_len; q.has_range = has_range;
     q.start = start; q.end = end;
     CtxDecodeBuffers B(c);
-    const int st = vcfc_dec::sparse_query(fd, q, B, c->stream, sink, (c->trace & VCFC_TRACE_SPARSE_QUERY) != 0);
+    const int st = vcfc_dec::sparse_query(fd, q, B, c->stream, FdSink{out_fd}, (c->trace & VCFC_TRACE_SPARSE_QUERY) != 0);
     close(fd);
     return st;
 }
@@ -1062,23 +1060,15 @@ int vcfc_query_binned_index_buffer(vcfc_ctx *c, const uint8_t *in, uint64_t n, c
         return VCFC_E_ARG;
     *out_len = 0;
     if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
-    uint64_t o = 0;
-    bool fits = true;
-    auto sink = [&](const uint8_t *p, uint64_t k) {
-        if (fits && o + k <= out_cap) memcpy(out + o, p, k);
-        else fits = false;
-        o += k;
-        return true;
-    };
+    BufferSink bs{out, out_cap};
     MemReader R(in, n);
     CtxDecodeBuffers B(c);
     vcfc_idx::QueryStats qs;
     const int st = vcfc_idx::query_index(R, index, index_bytes, reinterpret_cast<const uint8_t *>(ref), ref_len,
-                                         has_range, start, end, B, c->stream, sink, 4ull << 20, &qs);
+                                         has_range, start, end, B, c->stream, std::ref(bs), 4ull << 20, &qs);
     trace_index(c, qs, n);
-    *out_len = o;
-    if (!fits) return VCFC_E_NOSPACE;
-    return st;
+    *out_len = bs.o;
+    return bs.fits ? st : VCFC_E_NOSPACE;
 }
 
 int vcfc_query_binned_index_file(vcfc_ctx *c, const char *in_path, const char *index_path, const char *ref,
@@ -1092,20 +1082,11 @@ int vcfc_query_binned_index_file(vcfc_ctx *c, const char *in_path, const char *i
     if (fd < 0) return VCFC_E_IO;
     struct stat sb;
     if (fstat(fd, &sb) != 0) { close(fd); return VCFC_E_IO; }
-    auto sink = [&](const uint8_t *p, uint64_t k) {
-        while (k) {
-            const ssize_t w = write(out_fd, p, std::min<uint64_t>(k, 1ull << 30));
-            if (w <= 0) return false;
-            p += w;
-            k -= (uint64_t)w;
-        }
-        return true;
-    };
     FdReader R(fd, (uint64_t)sb.st_size);
     CtxDecodeBuffers B(c);
     vcfc_idx::QueryStats qs;
     st = vcfc_idx::query_index(R, idx.p, idx.n, reinterpret_cast<const uint8_t *>(ref), ref_len, has_range, start, end,
-                               B, c->stream, sink, 4ull << 20, &qs);
+                               B, c->stream, FdSink{out_fd}, 4ull << 20, &qs);
     trace_index(c, qs, (uint64_t)sb.st_size);
     close(fd);
     return st;
@@ -1193,21 +1174,12 @@ int vcfc_query_sparse_index_file(vcfc_ctx *c, const char *in_path, const char *i
         if (ifd >= 0) close(ifd);
         return VCFC_E_IO;
     }
-    auto sink = [&](const uint8_t *p, uint64_t k) {
-        while (k) {
-            const ssize_t w = write(out_fd, p, std::min<uint64_t>(k, 1ull << 30));
-            if (w <= 0) return false;
-            p += w;
-            k -= (uint64_t)w;
-        }
-        return true;
-    };
     FdReader R(fd, (uint64_t)sb.st_size);
     FdIndexFile I(ifd);
     CtxDecodeBuffers B(c);
     vcfc_idx::QueryStats qs;
     const int st = vcfc_spx::query_index(R, I, reinterpret_cast<const uint8_t *>(ref), ref_len, has_range, start, end, B,
-                                         c->stream, sink, 4ull << 20, &qs);
+                                         c->stream, FdSink{out_fd}, 4ull << 20, &qs);
     if (c->trace & VCFC_TRACE_INDEX)
         fprintf(stderr, "query_sparse_index: %llu windows, %llu bytes read of %llu, %llu records spanned\n",
                 (unsigned long long)qs.windows, (unsigned long long)qs.bytes, (unsigned long long)sb.st_size,
@@ -1258,14 +1230,9 @@ int vcfc_gap_analysis_file(vcfc_ctx *c, const char *in_path, const char *out_pat
     if ((st = vcfc_dec::parse_header(f.p, f.n, &data_off, nullptr))) return st;
     const int fd = open(out_path, O_CREAT | O_TRUNC | O_WRONLY, 0644);
     if (fd < 0) return VCFC_E_IO;
-    uint64_t o = 0;
-    auto sink = [&](const uint8_t *p, uint64_t k) {
-        if (write_all_at(fd, p, k, o) != VCFC_OK) return false;
-        o += k;
-        return true;
-    };
+    FileSink fs{fd};
     CtxDecodeBuffers B(c);
-    st = vcfc_spx::gap_analysis(f.p, f.n, B, c->stream, sink, nullptr);
+    st = vcfc_spx::gap_analysis(f.p, f.n, B, c->stream, std::ref(fs), nullptr);
     if (close(fd) != 0 && !st) st = VCFC_E_IO;
     return st;
 }
@@ -1273,17 +1240,46 @@ int vcfc_gap_analysis_file(vcfc_ctx *c, const char *in_path, const char *out_pat
 // ---- sample subset; drivers in vcfc_subset_driver.h ---------
 
 namespace {
-// header + sorted columns of a subset call; the status where either fails
-struct SubsetCall {
-    std::vector<uint8_t> hdr;
-    std::vector<uint32_t> csort, rank;
-    uint64_t data_off = 0, S = 0;
-    int prepare(const uint8_t *in, uint64_t n, const uint32_t *cols, uint64_t K) {
-        int st = vcfc_sub::subset_header(in, n, cols, K, hdr, &data_off, &S);
-        if (!st) st = vcfc_sub::sort_columns(cols, K, S, csort, rank);
-        return st;
-    }
-};
+// the lines (no header) of a prepared call over host bytes in[0, n): one
+// region's (q), else every record's (match == nullptr) or those `match` flags
+int subset_run(vcfc_ctx *c, const vcfc_sub::Call &sc, const uint8_t *in, uint64_t n, const vcfc_cnt::Query *q,
+               const vcfc_dec::MatchStep *match, const vcfc_dec::Sink &sink) {
+    CtxDecodeBuffers B(c);
+    in += sc.data_off;
+    n -= sc.data_off;
+    if (q)
+        return vcfc_sub::query_section(in, n, sc.S, sc.csort, sc.rank, q->ref, q->ref_len, q->has_range, q->start, q->end, B,
+                                       c->stream, sink);
+    if (match) return vcfc_sub::matched_section(in, n, sc.S, sc.csort, sc.rank, *match, B, c->stream, sink);
+    return vcfc_sub::decode_section(in, n, sc.S, sc.csort, sc.rank, B, c->stream, sink);
+}
+
+// header: the subset's header goes first (the whole-file decode)
+int subset_to_buffer(vcfc_ctx *c, const uint8_t *in, uint64_t n, const uint32_t *cols, uint64_t n_cols, bool header,
+                     const vcfc_cnt::Query *q, const vcfc_dec::MatchStep *match, uint8_t *out, uint64_t out_cap,
+                     uint64_t *out_len) {
+    *out_len = 0;
+    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
+    vcfc_sub::Call sc;
+    int st = sc.prepare(in, n, cols, n_cols);
+    if (st) return st;
+    BufferSink bs{out, out_cap};
+    if (header) bs(sc.hdr.data(), sc.hdr.size());
+    st = subset_run(c, sc, in, n, q, match, std::ref(bs));
+    *out_len = bs.o;
+    return bs.fits ? st : VCFC_E_NOSPACE;
+}
+
+int subset_to_fd(vcfc_ctx *c, const char *in_path, const uint32_t *cols, uint64_t n_cols, const vcfc_cnt::Query *q,
+                 const vcfc_dec::MatchStep *match, int out_fd) {
+    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
+    MappedFile f;
+    int st = f.open_ro(in_path);
+    if (st) return st;
+    vcfc_sub::Call sc;
+    if ((st = sc.prepare(f.p, f.n, cols, n_cols))) return st;
+    return subset_run(c, sc, f.p, f.n, q, match, FdSink{out_fd});
+}
 }  // namespace
 
 int vcfc_sample_columns(const uint8_t *in, uint64_t n, const char *names, uint64_t names_len, uint32_t *cols,
@@ -1297,25 +1293,7 @@ int vcfc_sample_columns(const uint8_t *in, uint64_t n, const char *names, uint64
 int vcfc_decompress_samples_buffer(vcfc_ctx *c, const uint8_t *in, uint64_t n, const uint32_t *cols, uint64_t n_cols,
                                    uint8_t *out, uint64_t out_cap, uint64_t *out_len) {
     if (!c || (!in && n) || (!out && out_cap) || !out_len) return VCFC_E_ARG;
-    *out_len = 0;
-    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
-    SubsetCall sc;
-    int st = sc.prepare(in, n, cols, n_cols);
-    if (st) return st;
-    uint64_t o = 0;
-    bool fits = true;
-    auto sink = [&](const uint8_t *p, uint64_t k) {
-        if (fits && o + k <= out_cap) memcpy(out + o, p, k);
-        else fits = false;
-        o += k;
-        return true;
-    };
-    sink(sc.hdr.data(), sc.hdr.size());
-    CtxDecodeBuffers B(c);
-    st = vcfc_sub::decode_section(in + sc.data_off, n - sc.data_off, sc.S, sc.csort, sc.rank, B, c->stream, sink);
-    *out_len = o;
-    if (!fits) return VCFC_E_NOSPACE;
-    return st;
+    return subset_to_buffer(c, in, n, cols, n_cols, true, nullptr, nullptr, out, out_cap, out_len);
 }
 
 int vcfc_decompress_samples_file(vcfc_ctx *c, const char *in_path, const char *out_path, const uint32_t *cols,
@@ -1325,21 +1303,12 @@ int vcfc_decompress_samples_file(vcfc_ctx *c, const char *in_path, const char *o
     MappedFile f;
     int st = f.open_ro(in_path);
     if (st) return st;
-    SubsetCall sc;
-    if ((st = sc.prepare(f.p, f.n, cols, n_cols))) return st;   // nothing written
+    vcfc_sub::Call sc;
+    if ((st = sc.prepare(f.p, f.n, cols, n_cols))) return st;   // nothing written: the output is opened after this
     const int fd = open(out_path, O_CREAT | O_TRUNC | O_WRONLY, 0644);
     if (fd < 0) return VCFC_E_IO;
-    uint64_t o = 0;
-    auto sink = [&](const uint8_t *p, uint64_t k) {
-        if (write_all_at(fd, p, k, o)) return false;
-        o += k;
-        return true;
-    };
-    if (!sink(sc.hdr.data(), sc.hdr.size())) st = VCFC_E_IO;
-    if (!st) {
-        CtxDecodeBuffers B(c);
-        st = vcfc_sub::decode_section(f.p + sc.data_off, f.n - sc.data_off, sc.S, sc.csort, sc.rank, B, c->stream, sink);
-    }
+    FileSink fs{fd};
+    st = fs(sc.hdr.data(), sc.hdr.size()) ? subset_run(c, sc, f.p, f.n, nullptr, nullptr, std::ref(fs)) : VCFC_E_IO;
     if (close(fd) != 0 && !st) st = VCFC_E_IO;
     return st;
 }
@@ -1348,50 +1317,15 @@ int vcfc_query_samples_buffer(vcfc_ctx *c, const uint8_t *in, uint64_t n, const 
                               int has_range, uint64_t start, uint64_t end, const uint32_t *cols, uint64_t n_cols,
                               uint8_t *out, uint64_t out_cap, uint64_t *out_len) {
     if (!c || (!in && n) || (!ref && ref_len) || (!out && out_cap) || !out_len) return VCFC_E_ARG;
-    *out_len = 0;
-    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
-    SubsetCall sc;
-    int st = sc.prepare(in, n, cols, n_cols);
-    if (st) return st;
-    uint64_t o = 0;
-    bool fits = true;
-    auto sink = [&](const uint8_t *p, uint64_t k) {
-        if (fits && o + k <= out_cap) memcpy(out + o, p, k);
-        else fits = false;
-        o += k;
-        return true;
-    };
-    CtxDecodeBuffers B(c);
-    st = vcfc_sub::query_section(in + sc.data_off, n - sc.data_off, sc.S, sc.csort, sc.rank,
-                                 reinterpret_cast<const uint8_t *>(ref), ref_len, has_range, start, end, B, c->stream,
-                                 sink);
-    *out_len = o;
-    if (!fits) return VCFC_E_NOSPACE;
-    return st;
+    const vcfc_cnt::Query q{reinterpret_cast<const uint8_t *>(ref), ref_len, has_range, start, end};
+    return subset_to_buffer(c, in, n, cols, n_cols, false, &q, nullptr, out, out_cap, out_len);
 }
 
 int vcfc_query_samples_file(vcfc_ctx *c, const char *in_path, const char *ref, uint64_t ref_len, int has_range,
                             uint64_t start, uint64_t end, const uint32_t *cols, uint64_t n_cols, int out_fd) {
     if (!c || !in_path || (!ref && ref_len) || out_fd < 0) return VCFC_E_ARG;
-    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
-    MappedFile f;
-    int st = f.open_ro(in_path);
-    if (st) return st;
-    SubsetCall sc;
-    if ((st = sc.prepare(f.p, f.n, cols, n_cols))) return st;
-    auto sink = [&](const uint8_t *p, uint64_t k) {
-        while (k) {
-            const ssize_t w = write(out_fd, p, std::min<uint64_t>(k, 1ull << 30));
-            if (w <= 0) return false;
-            p += w;
-            k -= (uint64_t)w;
-        }
-        return true;
-    };
-    CtxDecodeBuffers B(c);
-    return vcfc_sub::query_section(f.p + sc.data_off, f.n - sc.data_off, sc.S, sc.csort, sc.rank,
-                                   reinterpret_cast<const uint8_t *>(ref), ref_len, has_range, start, end, B, c->stream,
-                                   sink);
+    const vcfc_cnt::Query q{reinterpret_cast<const uint8_t *>(ref), ref_len, has_range, start, end};
+    return subset_to_fd(c, in_path, cols, n_cols, &q, nullptr, out_fd);
 }
 
 uint64_t vcfc_subset_workspace_size(uint64_t n_records, uint64_t n_cols) {
@@ -1405,22 +1339,8 @@ int vcfc_decode_samples_device(const uint8_t *d_in, uint64_t in_bytes, const uin
     if ((n && (!d_in || !d_rec_start || !d_out)) || !d_ws || !d_line_off || !d_err) return VCFC_E_ARG;
     std::vector<uint32_t> csort, rank;
     if (vcfc_sub::sort_columns(cols, n_cols, samples, csort, rank)) return VCFC_E_ARG;
-    const VcfcSubsetLayout L = vcfc_subset_workspace_layout(n, n_cols);
-    if (ws_bytes < L.total) return VCFC_E_NOSPACE;
-    uint8_t *ws = static_cast<uint8_t *>(d_ws);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    VcfcSubsetArgs a;
-    a.in = d_in; a.n_bytes = in_bytes; a.rec_start = d_rec_start; a.select = d_select; a.n = n; a.S = samples;
-    a.K = (uint32_t)n_cols; a.out = d_out; a.out_cap = out_cap; a.line_off = d_line_off;
-    vcfc_subset_args_workspace(a, ws, L);
-    a.err = d_err;
-    // csort and rank live on this frame: the stream has taken them when the synchronise returns
-    if (hipMemcpyAsync(ws + L.csort, csort.data(), 4 * n_cols, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(ws + L.rank, rank.data(), 4 * n_cols, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-        return VCFC_E_HIP;
-    if (vcfc_subset_plan(a, s) != hipSuccess) return VCFC_E_HIP;
-    return vcfc_subset_write(a, 0, n, s) == hipSuccess ? VCFC_OK : VCFC_E_HIP;
+    return vcfc_sub::records_device(vcfc_sub::SUBSET, d_in, in_bytes, d_rec_start, d_select, n, samples, csort, rank, d_out,
+                                    out_cap, d_line_off, d_ws, ws_bytes, d_err, static_cast<hipStream_t>(stream));
 }
 
 // ---- genotype counts; driver in vcfc_counts_driver.h -----------
@@ -1539,34 +1459,6 @@ int vcfc_regions_match_device(const uint8_t *d_in, const uint64_t *d_rec_start, 
                                           static_cast<hipStream_t>(stream));
 }
 
-namespace {
-// the sink of a buffer call: counts every byte, copies while they fit
-struct BufferSink {
-    uint8_t *out;
-    uint64_t cap, o = 0;
-    bool fits = true;
-    bool operator()(const uint8_t *p, uint64_t k) {
-        if (fits && o + k <= cap) memcpy(out + o, p, k);
-        else fits = false;
-        o += k;
-        return true;
-    }
-};
-// the sink of a call that writes to a descriptor
-struct FdSink {
-    int fd;
-    bool operator()(const uint8_t *p, uint64_t k) const {
-        while (k) {
-            const ssize_t w = write(fd, p, std::min<uint64_t>(k, 1ull << 30));
-            if (w <= 0) return false;
-            p += w;
-            k -= (uint64_t)w;
-        }
-        return true;
-    }
-};
-}  // namespace
-
 int vcfc_query_regions_buffer(vcfc_ctx *c, const uint8_t *in, uint64_t n, const uint8_t *table, uint64_t table_bytes,
                               uint8_t *out, uint64_t out_cap, uint64_t *out_len) {
     if (!c || (!in && n) || (!out && out_cap) || !out_len || !vcfc_reg::regions_validate(table, table_bytes))
@@ -1604,33 +1496,17 @@ int vcfc_query_samples_regions_buffer(vcfc_ctx *c, const uint8_t *in, uint64_t n
                                       uint64_t out_cap, uint64_t *out_len) {
     if (!c || (!in && n) || (!out && out_cap) || !out_len || !vcfc_reg::regions_validate(table, table_bytes))
         return VCFC_E_ARG;
-    *out_len = 0;
-    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
-    SubsetCall sc;
-    int st = sc.prepare(in, n, cols, n_cols);
-    if (st) return st;
-    BufferSink bs{out, out_cap};
     const uint8_t *d_table = nullptr;
-    CtxDecodeBuffers B(c);
-    st = vcfc_sub::matched_section(in + sc.data_off, n - sc.data_off, sc.S, sc.csort, sc.rank,
-                                   vcfc_reg::regions_step(table, table_bytes, &d_table), B, c->stream, std::ref(bs));
-    *out_len = bs.o;
-    return bs.fits ? st : VCFC_E_NOSPACE;
+    const vcfc_dec::MatchStep m = vcfc_reg::regions_step(table, table_bytes, &d_table);
+    return subset_to_buffer(c, in, n, cols, n_cols, false, nullptr, &m, out, out_cap, out_len);
 }
 
 int vcfc_query_samples_regions_file(vcfc_ctx *c, const char *in_path, const uint8_t *table, uint64_t table_bytes,
                                     const uint32_t *cols, uint64_t n_cols, int out_fd) {
     if (!c || !in_path || out_fd < 0 || !vcfc_reg::regions_validate(table, table_bytes)) return VCFC_E_ARG;
-    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
-    MappedFile f;
-    int st = f.open_ro(in_path);
-    if (st) return st;
-    SubsetCall sc;
-    if ((st = sc.prepare(f.p, f.n, cols, n_cols))) return st;
     const uint8_t *d_table = nullptr;
-    CtxDecodeBuffers B(c);
-    return vcfc_sub::matched_section(f.p + sc.data_off, f.n - sc.data_off, sc.S, sc.csort, sc.rank,
-                                     vcfc_reg::regions_step(table, table_bytes, &d_table), B, c->stream, FdSink{out_fd});
+    const vcfc_dec::MatchStep m = vcfc_reg::regions_step(table, table_bytes, &d_table);
+    return subset_to_fd(c, in_path, cols, n_cols, nullptr, &m, out_fd);
 }
 
 // ---- extract; driver in vcfc_extract_driver.h ---------------------
@@ -1728,23 +1604,8 @@ int vcfc_extract_samples_device(const uint8_t *d_in, uint64_t in_bytes, const ui
     if ((n && (!d_in || !d_rec_start || (!d_out && out_cap))) || !d_ws || !d_rec_off || !d_err) return VCFC_E_ARG;
     std::vector<uint32_t> csort, rank;
     if (vcfc_ext::device_columns(cols, n_cols, samples, csort, rank)) return VCFC_E_ARG;
-    const uint64_t K = csort.size();
-    const VcfcSubsetLayout L = vcfc_extract_workspace_layout(n, K);
-    if (ws_bytes < L.total) return VCFC_E_NOSPACE;
-    uint8_t *ws = static_cast<uint8_t *>(d_ws);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    VcfcExtractArgs a;
-    a.in = d_in; a.n_bytes = in_bytes; a.rec_start = d_rec_start; a.select = d_select; a.n = n; a.S = samples;
-    a.K = (uint32_t)K; a.out = d_out; a.out_cap = out_cap; a.line_off = d_rec_off;
-    vcfc_subset_args_workspace(a, ws, L);
-    a.err = d_err;
-    // csort and rank live on this frame: the stream has taken them when the synchronise returns
-    if (hipMemcpyAsync(ws + L.csort, csort.data(), 4 * K, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(ws + L.rank, rank.data(), 4 * K, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-        return VCFC_E_HIP;
-    if (vcfc_extract_plan(a, s) != hipSuccess) return VCFC_E_HIP;
-    return vcfc_extract_write(a, 0, n, s) == hipSuccess ? VCFC_OK : VCFC_E_HIP;
+    return vcfc_sub::records_device(vcfc_ext::EXTRACT, d_in, in_bytes, d_rec_start, d_select, n, samples, csort, rank, d_out,
+                                    out_cap, d_rec_off, d_ws, ws_bytes, d_err, static_cast<hipStream_t>(stream));
 }
 
 int vcfc_genotype_counts_regions_buffer(vcfc_ctx *c, const uint8_t *in, uint64_t n, const uint8_t *table,

@@ -4,13 +4,11 @@
 // both.
 //
 //   1. the header: S from the '#CHROM' line (ST_E_ARG for S == 0 or >= 2^30);
-//   2. hop the LEN headers on the host to find record starts;
-//   3. with a query, a match step (vcfc_dec::MatchStep: the range query's,
-//      kernel and error word unchanged, or a region table's)
-//      flags the records to count;
-//   4. the records in batches of rec_batch: one scan each gives the batch's
+//   2. vcfc_dec::open_section: record starts, and with a query the flags of
+//      the records to count, on the host too;
+//   3. the records in batches of rec_batch: one scan each gives the batch's
 //      rows and adds to the sample table, which stays on the device;
-//   5. ST_E_FORMAT at the first counted record that is not regular, at a match
+//   4. ST_E_FORMAT at the first counted record that is not regular, at a match
 //      error, or where hopping stopped with 8 or more bytes left: the rows
 //      before it are kept, the sample table is not.
 #pragma once
@@ -75,67 +73,45 @@ inline int counts_device(const uint8_t *d_in, uint64_t in_bytes, const uint64_t 
 inline int counts_section(const uint8_t *h_in, uint64_t n, uint64_t S, const vcfc_dec::MatchStep *q, Buffers &B,
                           hipStream_t s, Result &R, uint64_t rec_batch = 1ull << 22) {
     R = Result();
-    std::vector<uint64_t> rec;
-    vcfc_dec::hop(h_in, n, rec);
-    R.rec_start = rec;
-    const uint64_t nrec = rec.size() - 1;
-    const bool tail = n - rec.back() >= 8;   // fewer than 8 bytes left: a clean end
+    // the sample table is zeroed ahead of the match step, on a file with no record too
     uint64_t *d_sample = static_cast<uint64_t *>(B.get(Buffers::LINE_OFF, 40 * S));
     if (!d_sample || hipMemsetAsync(d_sample, 0, 40 * S, s) != hipSuccess) return ST_E_HIP;
-    uint64_t k = nrec;   // records [0, k) are to be counted
+    vcfc_dec::Section X;
     std::vector<uint8_t> flag;
-    if (nrec) {
-        const uint8_t *d_in = vcfc_dec::upload(B, Buffers::IN, h_in, n, s);
-        const uint64_t *d_rec = reinterpret_cast<const uint64_t *>(
-            vcfc_dec::upload(B, Buffers::REC, reinterpret_cast<const uint8_t *>(rec.data()), 8 * rec.size(), s));
-        if (!d_in || !d_rec) return ST_E_HIP;
-        const uint8_t *d_flag = nullptr;
-        if (q) {
-            const bool ready = q->prepare(B, s);
-            uint64_t *d_small = static_cast<uint64_t *>(B.get(Buffers::SMALL, 64));
-            uint8_t *d_f = static_cast<uint8_t *>(B.get(Buffers::FLAG, nrec + 64));
-            if (!ready || !d_small || !d_f) return ST_E_HIP;
-            uint64_t err = 0;
-            flag.resize(nrec);
-            if (q->run(d_in, d_rec, nrec, d_f, d_small, s) != hipSuccess ||
-                hipMemcpyAsync(&err, d_small, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
-                hipMemcpyAsync(flag.data(), d_f, nrec, hipMemcpyDeviceToHost, s) != hipSuccess ||
-                hipStreamSynchronize(s) != hipSuccess)
-                return ST_E_HIP;
-            if (err != VCFCD_NO_ERROR) k = err >> 8;   // the first record with a match error
-            d_flag = d_f;
+    const int st = vcfc_dec::open_section(h_in, n, q, B, s, X, &flag);
+    R.rec_start = X.rec;
+    if (st) return st;
+    const uint64_t nrec = X.nrec, k = X.k;   // records [0, k) are to be counted
+    for (uint64_t i0 = 0; i0 < k; i0 += rec_batch) {
+        const uint64_t nb = std::min(rec_batch, k - i0);
+        const VcfcCountsLayout L = vcfc_counts_workspace_layout(nb, S);
+        uint8_t *ws = static_cast<uint8_t *>(B.get(Buffers::WS, L.total));
+        uint32_t *d_rows = static_cast<uint32_t *>(B.get(Buffers::OUT, 32 * nb + 64));
+        if (!ws || !d_rows) return ST_E_HIP;
+        VcfcCountsArgs a;
+        a.in = X.d_in; a.n_bytes = n; a.rec_start = X.d_rec + i0; a.select = X.d_flag ? X.d_flag + i0 : nullptr; a.n = nb;
+        a.S = S; a.variant = d_rows; a.sample = d_sample;
+        vcfc_counts_args_workspace(a, ws, L);
+        uint64_t err = 0;
+        if (vcfc_counts_run(a, s) != hipSuccess || hipMemcpyAsync(&err, a.err, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess)
+            return ST_E_HIP;
+        const uint64_t good = err == VCFCD_NO_ERROR ? nb : err >> 8;
+        std::vector<uint32_t> rows(8 * good);
+        if (good && (hipMemcpyAsync(rows.data(), d_rows, 32 * good, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                     hipStreamSynchronize(s) != hipSuccess))
+            return ST_E_HIP;
+        for (uint64_t j = 0; j < good; j++) {
+            if (q && !flag[i0 + j]) continue;
+            R.index.push_back(i0 + j);
+            R.rows.insert(R.rows.end(), rows.begin() + 8 * j, rows.begin() + 8 * j + 8);
         }
-        for (uint64_t i0 = 0; i0 < k; i0 += rec_batch) {
-            const uint64_t nb = std::min(rec_batch, k - i0);
-            const VcfcCountsLayout L = vcfc_counts_workspace_layout(nb, S);
-            uint8_t *ws = static_cast<uint8_t *>(B.get(Buffers::WS, L.total));
-            uint32_t *d_rows = static_cast<uint32_t *>(B.get(Buffers::OUT, 32 * nb + 64));
-            if (!ws || !d_rows) return ST_E_HIP;
-            VcfcCountsArgs a;
-            a.in = d_in; a.n_bytes = n; a.rec_start = d_rec + i0; a.select = d_flag ? d_flag + i0 : nullptr; a.n = nb;
-            a.S = S; a.variant = d_rows; a.sample = d_sample;
-            vcfc_counts_args_workspace(a, ws, L);
-            uint64_t err = 0;
-            if (vcfc_counts_run(a, s) != hipSuccess || hipMemcpyAsync(&err, a.err, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
-                hipStreamSynchronize(s) != hipSuccess)
-                return ST_E_HIP;
-            const uint64_t good = err == VCFCD_NO_ERROR ? nb : err >> 8;
-            std::vector<uint32_t> rows(8 * good);
-            if (good && (hipMemcpyAsync(rows.data(), d_rows, 32 * good, hipMemcpyDeviceToHost, s) != hipSuccess ||
-                         hipStreamSynchronize(s) != hipSuccess))
-                return ST_E_HIP;
-            for (uint64_t j = 0; j < good; j++) {
-                if (q && !flag[i0 + j]) continue;
-                R.index.push_back(i0 + j);
-                R.rows.insert(R.rows.end(), rows.begin() + 8 * j, rows.begin() + 8 * j + 8);
-            }
-            if (good < nb) {
-                R.err_record = i0 + good;
-                return ST_E_FORMAT;
-            }
+        if (good < nb) {
+            R.err_record = i0 + good;
+            return ST_E_FORMAT;
         }
     }
-    if (k < nrec || tail) {
+    if (k < nrec || X.tail()) {
         R.err_record = k;
         return ST_E_FORMAT;
     }

@@ -224,30 +224,12 @@ inline uint8_t *upload(Buffers &B, int slot, const uint8_t *h, uint64_t n, hipSt
     return d;
 }
 
-// Decode a .vcfc data section (host bytes h_in[0, n); uploaded here).
-inline int decode_section(const uint8_t *h_in, uint64_t n, uint64_t S, Buffers &B, hipStream_t s, const Sink &sink,
-                          uint64_t out_batch = 1ull << 30) {
-    std::vector<uint64_t> rec;
-    hop(h_in, n, rec);
-    const uint8_t *d_in = upload(B, Buffers::IN, h_in, n, s);
-    const uint64_t *d_rec = reinterpret_cast<const uint64_t *>(
-        upload(B, Buffers::REC, reinterpret_cast<const uint8_t *>(rec.data()), 8 * rec.size(), s));
-    if (!d_in || !d_rec) return ST_E_HIP;
-    int stop = 0;
-    uint64_t p_stream = rec.back();   // byte-serial continuation point
-    int st = decode_records(d_in, n, S, d_rec, nullptr, rec.size() - 1, B, s, sink, out_batch, &stop, &p_stream);
-    if (st) return st;
-    if (stop == 1) return ST_E_FORMAT;
-    if (n - p_stream < 8) return ST_OK;   // clean end (:768-774)
-    return stream_tail(B, s, sink, [&](uint8_t *out, uint64_t *dst) { return vcfc_decode_stream(d_in, n, p_stream, S, ~0ull, out, dst, s); });
-}
-
 // The match step of a query: who fills the flags.  prepare uploads what the
 // match reads (false: ST_E_HIP); run enqueues the match of records
 // [d_rec[i], d_rec[i + 1]), i < nrec: d_flag[i], and *d_err = the minimum
-// over records of (i << 8 | code) as vcfc_query_match defines it.  The
-// drivers of the selected decode, the subset decode and the counts take it,
-// so one region and a region table share their bodies.
+// over records of (i << 8 | code) as vcfc_query_match defines it.  Every
+// driver that walks a section takes one, so one region and a region table
+// share their bodies.
 struct MatchStep {
     std::function<bool(Buffers &, hipStream_t)> prepare;
     std::function<hipError_t(const uint8_t *d_in, const uint64_t *d_rec, uint64_t nrec, uint8_t *d_flag, uint64_t *d_err,
@@ -267,45 +249,85 @@ inline MatchStep region_step(const uint8_t *qref, uint64_t qref_len, int has_ran
     return m;
 }
 
-// What matched_records leaves for its caller.
-struct Matched {
+// A data section on the device, as open_section leaves it.
+struct Section {
     std::vector<uint64_t> rec;   // the hopped record starts; back() = where hopping stopped
+    uint64_t n = 0, nrec = 0;    // the section's bytes, its hopped records
     const uint8_t *d_in = nullptr;
-    uint64_t nrec = 0;
+    const uint64_t *d_rec = nullptr;
+    uint8_t *d_flag = nullptr;   // null without a match
+    uint64_t *d_small = nullptr; // the SMALL slot (64 bytes), free for the caller's own error word
     uint64_t err = VCFCD_NO_ERROR;   // the match's error word
-    uint64_t k = 0;              // records before the first match error
-    int stop = 0;                // decode_records' verdict over records [0, k)
+    uint64_t k = 0;              // records before the first match error (nrec without a match)
+    bool tail() const { return n - rec.back() >= 8; }   // fewer than 8 bytes left after the last hop: a clean end
+};
+
+// The prologue of every driver that walks a data section (host bytes
+// h_in[0, n)): hop the LEN headers, upload the section and the record starts,
+// run `match` (nullable) into the flags and read its error word.  Gets the
+// slots IN, SMALL, REC, FLAG and (through match->prepare) QREF, each once, and
+// no other; REC, FLAG and the match run are left out where nothing hopped.
+// h_flag (optional): the flags on the host too, in the same synchronise.
+inline int open_section(const uint8_t *h_in, uint64_t n, const MatchStep *match, Buffers &B, hipStream_t s, Section &X,
+                        std::vector<uint8_t> *h_flag = nullptr) {
+    hop(h_in, n, X.rec);
+    X.n = n;
+    X.nrec = X.k = X.rec.size() - 1;
+    X.d_in = upload(B, Buffers::IN, h_in, n, s);
+    const bool ready = !match || match->prepare(B, s);
+    X.d_small = static_cast<uint64_t *>(B.get(Buffers::SMALL, 64));
+    if (!X.d_in || !ready || !X.d_small) return ST_E_HIP;
+    if (!X.nrec) return ST_OK;
+    X.d_rec = reinterpret_cast<const uint64_t *>(
+        upload(B, Buffers::REC, reinterpret_cast<const uint8_t *>(X.rec.data()), 8 * (X.nrec + 1), s));
+    if (!X.d_rec) return ST_E_HIP;
+    if (!match) return ST_OK;
+    X.d_flag = static_cast<uint8_t *>(B.get(Buffers::FLAG, X.nrec + 64));
+    if (!X.d_flag) return ST_E_HIP;
+    if (h_flag) h_flag->resize(X.nrec);
+    if (match->run(X.d_in, X.d_rec, X.nrec, X.d_flag, X.d_small, s) != hipSuccess ||
+        hipMemcpyAsync(&X.err, X.d_small, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        (h_flag && hipMemcpyAsync(h_flag->data(), X.d_flag, X.nrec, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return ST_E_HIP;
+    if (X.err != VCFCD_NO_ERROR) X.k = X.err >> 8;   // records [0, k) come before the first match error
+    return ST_OK;
+}
+
+// Decode a .vcfc data section (host bytes h_in[0, n); uploaded here).
+inline int decode_section(const uint8_t *h_in, uint64_t n, uint64_t S, Buffers &B, hipStream_t s, const Sink &sink,
+                          uint64_t out_batch = 1ull << 30) {
+    Section X;
+    int st = open_section(h_in, n, nullptr, B, s, X);
+    if (st) return st;
+    int stop = 0;
+    uint64_t p_stream = X.rec.back();   // byte-serial continuation point
+    st = decode_records(X.d_in, n, S, X.d_rec, nullptr, X.nrec, B, s, sink, out_batch, &stop, &p_stream);
+    if (st) return st;
+    if (stop == 1) return ST_E_FORMAT;
+    if (n - p_stream < 8) return ST_OK;   // clean end (:768-774)
+    const uint8_t *d_in = X.d_in;
+    return stream_tail(B, s, sink, [&](uint8_t *out, uint64_t *dst) { return vcfc_decode_stream(d_in, n, p_stream, S, ~0ull, out, dst, s); });
+}
+
+// open_section with a match, then the flagged records before the first match
+// error decoded through decode_records: its verdict over records [0, k).
+struct Matched : Section {
+    int stop = 0;
     uint64_t cont = 0;
 };
 
-// Steps 1 and 2 of a query over a data section: hop the LEN headers, fill the
-// flags with `match`, decode the flagged records before the first match
-// error through decode_records.
 inline int matched_records(const uint8_t *h_in, uint64_t n, uint64_t S, const MatchStep &match, Buffers &B, hipStream_t s,
                            const Sink &sink, uint64_t out_batch, bool strict, Matched &M) {
-    hop(h_in, n, M.rec);
-    M.nrec = M.k = M.rec.size() - 1;
-    M.d_in = upload(B, Buffers::IN, h_in, n, s);
-    const bool ready = match.prepare(B, s);
-    uint64_t *d_small = static_cast<uint64_t *>(B.get(Buffers::SMALL, 64));
-    if (!M.d_in || !ready || !d_small) return ST_E_HIP;
-    if (!M.nrec) return ST_OK;
-    const uint64_t *d_rec = reinterpret_cast<const uint64_t *>(
-        upload(B, Buffers::REC, reinterpret_cast<const uint8_t *>(M.rec.data()), 8 * (M.nrec + 1), s));
-    uint8_t *d_flag = static_cast<uint8_t *>(B.get(Buffers::FLAG, M.nrec + 64));
-    if (!d_rec || !d_flag) return ST_E_HIP;
-    if (match.run(M.d_in, d_rec, M.nrec, d_flag, d_small, s) != hipSuccess ||
-        hipMemcpyAsync(&M.err, d_small, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return ST_E_HIP;
-    // records before the first irregular one k: the matching ones decode
-    if (M.err != VCFCD_NO_ERROR) M.k = M.err >> 8;
-    return decode_records(M.d_in, n, S, d_rec, d_flag, M.k, B, s, sink, out_batch, &M.stop, &M.cont, nullptr, strict);
+    const int st = open_section(h_in, n, &match, B, s, M);
+    if (st) return st;
+    return decode_records(M.d_in, n, S, M.d_rec, M.d_flag, M.k, B, s, sink, out_batch, &M.stop, &M.cont, nullptr, strict);
 }
 
 // Range query over a .vcfc data section (query_compressed_file, reference
 // src/main.cpp:3777-3929): the matching lines, no header.
-//   1. hop the LEN headers; one lane per record finds CHROM/POS and the
-//      match flag (k_query_match);
+//   1. open_section: one lane per record finds CHROM/POS and the match flag
+//      (k_query_match);
 //   2. the records before the first irregular one decode through
 //      decode_records, the flags selecting the matching ones;
 //   3. from the first record where the reference's walk leaves the hops (a
@@ -347,7 +369,7 @@ inline int query_regions_section(const uint8_t *h_in, uint64_t n, uint64_t S, co
     const int st = matched_records(h_in, n, S, match, B, s, sink, out_batch, true, M);
     if (st) return st;
     if (M.stop || M.k < M.nrec) return ST_E_FORMAT;
-    return n - M.rec.back() >= 8 ? ST_E_FORMAT : ST_OK;   // fewer than 8 bytes left: a clean end
+    return M.tail() ? ST_E_FORMAT : ST_OK;
 }
 
 

@@ -4,12 +4,11 @@
 // both.
 //
 //   1. the header: S from the '#CHROM' line (ST_E_ARG for S == 0 or >= 2^30);
-//   2. hop the LEN headers on the host to find record starts;
-//   3. with a query, a match step (vcfc_dec::MatchStep: the range query's, or
-//      a region table's) flags the records that get a row;
-//   4. the records in batches of rec_batch: one pass each writes the batch's
+//   2. vcfc_dec::open_section: record starts, and with a query the flags of
+//      the records that get a row, on the host too;
+//   3. the records in batches of rec_batch: one pass each writes the batch's
 //      rows densely on the device;
-//   5. ST_E_FORMAT at the first selected record that is not regular, at a
+//   4. ST_E_FORMAT at the first selected record that is not regular, at a
 //      match error, or where hopping stopped with 8 or more bytes left: the
 //      rows before it are kept.
 #pragma once
@@ -68,65 +67,42 @@ inline int matrix_section(const uint8_t *h_in, uint64_t n, uint64_t S, int layou
     const uint64_t rb = vcfc_matrix_row_size(layout, S);
     if (!rb) return ST_E_ARG;
     if (!rec_batch) rec_batch = default_batch(rb);
-    std::vector<uint64_t> rec;
-    vcfc_dec::hop(h_in, n, rec);
-    R.rec_start = rec;
-    const uint64_t nrec = rec.size() - 1;
-    const bool tail = n - rec.back() >= 8;   // fewer than 8 bytes left: a clean end
-    uint64_t k = nrec;   // records [0, k) are to be looked at
+    vcfc_dec::Section X;
     std::vector<uint8_t> flag;
-    if (nrec) {
-        const uint8_t *d_in = vcfc_dec::upload(B, Buffers::IN, h_in, n, s);
-        const uint64_t *d_rec = reinterpret_cast<const uint64_t *>(
-            vcfc_dec::upload(B, Buffers::REC, reinterpret_cast<const uint8_t *>(rec.data()), 8 * rec.size(), s));
-        uint64_t *d_small = static_cast<uint64_t *>(B.get(Buffers::SMALL, 64));
-        if (!d_in || !d_rec || !d_small) return ST_E_HIP;
-        const uint8_t *d_flag = nullptr;
-        if (q) {
-            const bool ready = q->prepare(B, s);
-            uint8_t *d_f = static_cast<uint8_t *>(B.get(Buffers::FLAG, nrec + 64));
-            if (!ready || !d_f) return ST_E_HIP;
-            uint64_t err = 0;
-            flag.resize(nrec);
-            if (q->run(d_in, d_rec, nrec, d_f, d_small, s) != hipSuccess ||
-                hipMemcpyAsync(&err, d_small, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
-                hipMemcpyAsync(flag.data(), d_f, nrec, hipMemcpyDeviceToHost, s) != hipSuccess ||
-                hipStreamSynchronize(s) != hipSuccess)
-                return ST_E_HIP;
-            if (err != VCFCD_NO_ERROR) k = err >> 8;   // the first record with a match error
-            d_flag = d_f;
-        }
-        std::vector<uint64_t> row_of;
-        for (uint64_t i0 = 0; i0 < k; i0 += rec_batch) {
-            const uint64_t nb = std::min(rec_batch, k - i0);
-            const VcfcMatrixLayout L = vcfc_matrix_workspace_layout(nb);
-            void *ws = B.get(Buffers::WS, L.total);
-            uint8_t *d_rows = static_cast<uint8_t *>(B.get(Buffers::OUT, nb * rb + 64));
-            uint64_t *d_row_of = static_cast<uint64_t *>(B.get(Buffers::LINE_OFF, 8 * (nb + 1)));
-            if (!ws || !d_rows || !d_row_of) return ST_E_HIP;
-            uint64_t err = 0;
-            row_of.resize(nb + 1);
-            if (matrix_device(d_in, n, d_rec + i0, d_flag ? d_flag + i0 : nullptr, nb, S, layout, d_rows, nb * rb, rb, d_row_of,
-                              ws, L.total, d_small, s) != ST_OK ||
-                hipMemcpyAsync(&err, d_small, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
-                hipMemcpyAsync(row_of.data(), d_row_of, 8 * (nb + 1), hipMemcpyDeviceToHost, s) != hipSuccess ||
-                hipStreamSynchronize(s) != hipSuccess)
-                return ST_E_HIP;
-            const uint64_t good = err == VCFCD_NO_ERROR ? nb : err >> 8;
-            const uint64_t rows = row_of[good], have = R.rows.size();
-            R.rows.resize(have + rows * rb);
-            if (rows && (hipMemcpyAsync(R.rows.data() + have, d_rows, rows * rb, hipMemcpyDeviceToHost, s) != hipSuccess ||
-                         hipStreamSynchronize(s) != hipSuccess))
-                return ST_E_HIP;
-            for (uint64_t j = 0; j < good; j++)
-                if (!q || flag[i0 + j]) R.index.push_back(i0 + j);
-            if (good < nb) {
-                R.err_record = i0 + good;
-                return ST_E_FORMAT;
-            }
+    const int st = vcfc_dec::open_section(h_in, n, q, B, s, X, &flag);
+    R.rec_start = X.rec;
+    if (st) return st;
+    const uint64_t nrec = X.nrec, k = X.k;   // records [0, k) are to be looked at
+    std::vector<uint64_t> row_of;
+    for (uint64_t i0 = 0; i0 < k; i0 += rec_batch) {
+        const uint64_t nb = std::min(rec_batch, k - i0);
+        const VcfcMatrixLayout L = vcfc_matrix_workspace_layout(nb);
+        void *ws = B.get(Buffers::WS, L.total);
+        uint8_t *d_rows = static_cast<uint8_t *>(B.get(Buffers::OUT, nb * rb + 64));
+        uint64_t *d_row_of = static_cast<uint64_t *>(B.get(Buffers::LINE_OFF, 8 * (nb + 1)));
+        if (!ws || !d_rows || !d_row_of) return ST_E_HIP;
+        uint64_t err = 0;
+        row_of.resize(nb + 1);
+        if (matrix_device(X.d_in, n, X.d_rec + i0, X.d_flag ? X.d_flag + i0 : nullptr, nb, S, layout, d_rows, nb * rb, rb,
+                          d_row_of, ws, L.total, X.d_small, s) != ST_OK ||
+            hipMemcpyAsync(&err, X.d_small, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipMemcpyAsync(row_of.data(), d_row_of, 8 * (nb + 1), hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess)
+            return ST_E_HIP;
+        const uint64_t good = err == VCFCD_NO_ERROR ? nb : err >> 8;
+        const uint64_t rows = row_of[good], have = R.rows.size();
+        R.rows.resize(have + rows * rb);
+        if (rows && (hipMemcpyAsync(R.rows.data() + have, d_rows, rows * rb, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                     hipStreamSynchronize(s) != hipSuccess))
+            return ST_E_HIP;
+        for (uint64_t j = 0; j < good; j++)
+            if (!q || flag[i0 + j]) R.index.push_back(i0 + j);
+        if (good < nb) {
+            R.err_record = i0 + good;
+            return ST_E_FORMAT;
         }
     }
-    if (k < nrec || tail) {
+    if (k < nrec || X.tail()) {
         R.err_record = k;
         return ST_E_FORMAT;
     }

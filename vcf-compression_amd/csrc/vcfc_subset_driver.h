@@ -5,14 +5,15 @@
 //
 //   1. the header: '##' lines verbatim, the '#CHROM' line cut to its first 9
 //      fields and the chosen names;
-//   2. hop the LEN headers on the host to find record starts;
-//   3. plan every record on the GPU exactly (line sizes, first irregular one);
+//   2. vcfc_dec::open_section: record starts, and with a query the flags of
+//      the matching records (vcfc_dec::MatchStep: the range query's, kernel
+//      and error word unchanged, or a region table's);
+//   3. plan every taken record on the GPU exactly (line sizes, first
+//      irregular one);
 //   4. write the lines before it in output batches;
-//   5. VCFC_E_FORMAT at the first record that is not regular, or where
-//      hopping stopped with 8 or more bytes left.
-// The query variants run a match step first (vcfc_dec::MatchStep: the range
-// query's, kernel and error word unchanged, or a region table's, DESIGN.md
-// §4k) and decode the matching records only.
+//   5. VCFC_E_FORMAT at that record, at a match error, or where hopping
+//      stopped with 8 or more bytes left.
+// Extract (vcfc_extract_driver.h) runs steps 2 to 5 with its own kernels.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -43,6 +44,17 @@ inline int sort_columns(const uint32_t *cols, uint64_t K, uint64_t S, std::vecto
     for (uint64_t k = 1; k < K; k++)
         if (csort[k] == csort[k - 1]) return ST_E_ARG;
     return ST_OK;
+}
+
+// sort_columns of the list, or, where the caller allows it (extract), of
+// 0 .. S - 1 for cols == nullptr and K == 0.
+inline int choose_columns(const uint32_t *cols, uint64_t K, uint64_t S, bool all_ok, std::vector<uint32_t> &csort,
+                          std::vector<uint32_t> &rank) {
+    if (cols || K || !all_ok) return sort_columns(cols, K, S, csort, rank);
+    if (S == 0 || S >= (1ull << 31)) return ST_E_ARG;
+    std::vector<uint32_t> all(S);
+    std::iota(all.begin(), all.end(), 0u);
+    return sort_columns(all.data(), S, S, csort, rank);
 }
 
 // The fields of the '#CHROM' line of a header parse_header accepts:
@@ -77,17 +89,72 @@ inline int subset_header(const uint8_t *in, uint64_t n, const uint32_t *cols, ui
     return ST_OK;
 }
 
-// The lines of the records [rec[i], rec[i + 1]), i < nrec, of the uploaded
-// data section (d_select, nullable: records with select[i] == 0 get no line
-// and are not checked), sunk in order.  *stop = 1: a record is not regular;
-// the lines before it are sunk.
-inline int subset_records(const uint8_t *d_in, uint64_t n, uint64_t S, const uint64_t *d_rec, const uint8_t *d_select,
-                          uint64_t nrec, const std::vector<uint32_t> &csort, const std::vector<uint32_t> &rank,
-                          Buffers &B, hipStream_t s, const Sink &sink, uint64_t out_batch, int *stop) {
+// Header and sorted columns of a whole-file call.  all_ok (extract): cols ==
+// nullptr and K == 0 keep the header verbatim and every column.
+struct Call {
+    std::vector<uint8_t> hdr;
+    std::vector<uint32_t> csort, rank;
+    uint64_t data_off = 0, S = 0;
+    int prepare(const uint8_t *in, uint64_t n, const uint32_t *cols, uint64_t K, bool all_ok = false) {
+        if (all_ok && !cols && K == 0) {
+            const int st = vcfc_dec::parse_header(in, n, &data_off, &S);
+            if (st) return st;
+            hdr.assign(in, in + data_off);
+        } else {
+            const int st = subset_header(in, n, cols, K, hdr, &data_off, &S);
+            if (st) return st;
+        }
+        return choose_columns(cols, K, S, all_ok, csort, rank);
+    }
+};
+
+// The three entry points in which the sample-subset decoder and extract
+// differ (vcfc_device.h); both use VcfcSubsetArgs and VcfcSubsetLayout.
+struct Kernels {
+    VcfcSubsetLayout (*layout)(uint64_t n, uint64_t K);
+    hipError_t (*plan)(const VcfcSubsetArgs &a, hipStream_t s);
+    hipError_t (*write)(const VcfcSubsetArgs &a, uint64_t first, uint64_t last, hipStream_t s);
+};
+constexpr Kernels SUBSET = {vcfc_subset_workspace_layout, vcfc_subset_plan, vcfc_subset_write};
+
+// The body of the two device entries (include/vcfc.h: vcfc_decode_samples_device,
+// vcfc_extract_samples_device) behind their pointer and column checks: the
+// workspace check, then plan and write enqueued on s.
+inline int records_device(const Kernels &kn, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_rec,
+                          const uint8_t *d_select, uint64_t n, uint64_t S, const std::vector<uint32_t> &csort,
+                          const std::vector<uint32_t> &rank, uint8_t *d_out, uint64_t out_cap, uint64_t *d_off, void *d_ws,
+                          uint64_t ws_bytes, uint64_t *d_err, hipStream_t s) {
+    const uint64_t K = csort.size();
+    const VcfcSubsetLayout L = kn.layout(n, K);
+    if (ws_bytes < L.total) return 4;   // VCFC_E_NOSPACE
+    uint8_t *ws = static_cast<uint8_t *>(d_ws);
+    VcfcSubsetArgs a;
+    a.in = d_in; a.n_bytes = in_bytes; a.rec_start = d_rec; a.select = d_select; a.n = n; a.S = S; a.K = (uint32_t)K;
+    a.out = d_out; a.out_cap = out_cap; a.line_off = d_off;
+    vcfc_subset_args_workspace(a, ws, L);
+    a.err = d_err;
+    // csort and rank live on the caller's frame: the stream has taken them when the synchronise returns
+    if (hipMemcpyAsync(ws + L.csort, csort.data(), 4 * K, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(ws + L.rank, rank.data(), 4 * K, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return ST_E_HIP;
+    if (kn.plan(a, s) != hipSuccess) return ST_E_HIP;
+    return kn.write(a, 0, n, s) == hipSuccess ? ST_OK : ST_E_HIP;
+}
+
+// The output (kn: lines, or extract's records) of the records [rec[i],
+// rec[i + 1]), i < nrec, of the uploaded data section (d_select, nullable:
+// records with select[i] == 0 give nothing and are not checked), sunk in
+// order.  *stop = 1: a record is not regular (extract: or not re-encodable);
+// the output before it is sunk.
+inline int subset_records(const Kernels &kn, const uint8_t *d_in, uint64_t n, uint64_t S, const uint64_t *d_rec,
+                          const uint8_t *d_select, uint64_t nrec, const std::vector<uint32_t> &csort,
+                          const std::vector<uint32_t> &rank, Buffers &B, hipStream_t s, const Sink &sink, uint64_t out_batch,
+                          int *stop) {
     *stop = 0;
     if (!nrec) return ST_OK;
     const uint64_t K = csort.size();
-    const VcfcSubsetLayout L = vcfc_subset_workspace_layout(nrec, K);
+    const VcfcSubsetLayout L = kn.layout(nrec, K);
     uint8_t *ws = static_cast<uint8_t *>(B.get(Buffers::WS, L.total));
     uint64_t *d_loff = static_cast<uint64_t *>(B.get(Buffers::LINE_OFF, 8 * (nrec + 1)));
     if (!ws || !d_loff) return ST_E_HIP;
@@ -99,7 +166,7 @@ inline int subset_records(const uint8_t *d_in, uint64_t n, uint64_t S, const uin
         hipMemcpyAsync(ws + L.rank, rank.data(), 4 * K, hipMemcpyHostToDevice, s) != hipSuccess)
         return ST_E_HIP;
     uint64_t err = 0;
-    if (vcfc_subset_plan(a, s) != hipSuccess || hipMemcpyAsync(&err, a.err, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+    if (kn.plan(a, s) != hipSuccess || hipMemcpyAsync(&err, a.err, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
         return ST_E_HIP;
     uint64_t n_lines = nrec;
@@ -121,7 +188,7 @@ inline int subset_records(const uint8_t *d_in, uint64_t n, uint64_t S, const uin
             if (!d_out || !host) return ST_E_HIP;
             a.out = d_out - loff[i0];   // lines are written at out + line_off[i]
             a.out_cap = loff[i1];
-            if (vcfc_subset_write(a, i0, i1, s) != hipSuccess ||
+            if (kn.write(a, i0, i1, s) != hipSuccess ||
                 hipMemcpyAsync(host, d_out, bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
                 hipStreamSynchronize(s) != hipSuccess)
                 return ST_E_HIP;
@@ -132,54 +199,36 @@ inline int subset_records(const uint8_t *d_in, uint64_t n, uint64_t S, const uin
     return ST_OK;
 }
 
-// The data section of a .vcfc (host bytes h_in[0, n); uploaded here).
+// The output (no header) of a .vcfc data section (host bytes h_in[0, n);
+// uploaded by vcfc_dec::open_section): of every record (match == nullptr), or
+// of those `match` flags (one region, or a region table); only taken records
+// must be regular.  ST_E_FORMAT at the first one that is not, at a match error
+// at record k (the output of the records before it sunk), or where hopping
+// stopped with 8 or more bytes left.
+inline int subset_section(const Kernels &kn, const uint8_t *h_in, uint64_t n, uint64_t S, const std::vector<uint32_t> &csort,
+                          const std::vector<uint32_t> &rank, const vcfc_dec::MatchStep *match, Buffers &B, hipStream_t s,
+                          const Sink &sink, uint64_t out_batch = 1ull << 30) {
+    vcfc_dec::Section X;
+    int st = vcfc_dec::open_section(h_in, n, match, B, s, X);
+    if (st) return st;
+    int stop = 0;
+    st = subset_records(kn, X.d_in, n, S, X.d_rec, X.d_flag, X.k, csort, rank, B, s, sink, out_batch, &stop);
+    if (st) return st;
+    return stop || X.k < X.nrec || X.tail() ? ST_E_FORMAT : ST_OK;
+}
+
+// The subset decoder's two names for subset_section with its own kernels, as
+// vcfc_ext::extract_section is extract's: every record's lines, and the lines
+// of the records `match` flags.
 inline int decode_section(const uint8_t *h_in, uint64_t n, uint64_t S, const std::vector<uint32_t> &csort,
                           const std::vector<uint32_t> &rank, Buffers &B, hipStream_t s, const Sink &sink,
                           uint64_t out_batch = 1ull << 30) {
-    std::vector<uint64_t> rec;
-    vcfc_dec::hop(h_in, n, rec);
-    const uint64_t nrec = rec.size() - 1;
-    if (nrec) {
-        const uint8_t *d_in = vcfc_dec::upload(B, Buffers::IN, h_in, n, s);
-        const uint64_t *d_rec = reinterpret_cast<const uint64_t *>(
-            vcfc_dec::upload(B, Buffers::REC, reinterpret_cast<const uint8_t *>(rec.data()), 8 * rec.size(), s));
-        if (!d_in || !d_rec) return ST_E_HIP;
-        int stop = 0;
-        const int st = subset_records(d_in, n, S, d_rec, nullptr, nrec, csort, rank, B, s, sink, out_batch, &stop);
-        if (st) return st;
-        if (stop) return ST_E_FORMAT;
-    }
-    return n - rec.back() >= 8 ? ST_E_FORMAT : ST_OK;   // fewer than 8 bytes left: a clean end
+    return subset_section(SUBSET, h_in, n, S, csort, rank, nullptr, B, s, sink, out_batch);
 }
-
-// The lines (no header) of the records `match` flags (vcfc_dec::MatchStep: one
-// region, or a region table); only flagged records must be regular.  A match
-// error at record k stops there.
 inline int matched_section(const uint8_t *h_in, uint64_t n, uint64_t S, const std::vector<uint32_t> &csort,
                            const std::vector<uint32_t> &rank, const vcfc_dec::MatchStep &match, Buffers &B, hipStream_t s,
                            const Sink &sink, uint64_t out_batch = 1ull << 30) {
-    std::vector<uint64_t> rec;
-    vcfc_dec::hop(h_in, n, rec);
-    const uint64_t nrec = rec.size() - 1;
-    if (nrec) {
-        const uint8_t *d_in = vcfc_dec::upload(B, Buffers::IN, h_in, n, s);
-        const bool ready = match.prepare(B, s);
-        uint64_t *d_small = static_cast<uint64_t *>(B.get(Buffers::SMALL, 64));
-        const uint64_t *d_rec = reinterpret_cast<const uint64_t *>(
-            vcfc_dec::upload(B, Buffers::REC, reinterpret_cast<const uint8_t *>(rec.data()), 8 * rec.size(), s));
-        uint8_t *d_flag = static_cast<uint8_t *>(B.get(Buffers::FLAG, nrec + 64));
-        if (!d_in || !ready || !d_small || !d_rec || !d_flag) return ST_E_HIP;
-        uint64_t err = 0;
-        if (match.run(d_in, d_rec, nrec, d_flag, d_small, s) != hipSuccess ||
-            hipMemcpyAsync(&err, d_small, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-            return ST_E_HIP;
-        const uint64_t k = err == VCFCD_NO_ERROR ? nrec : err >> 8;   // the first record with a match error
-        int stop = 0;
-        const int st = subset_records(d_in, n, S, d_rec, d_flag, k, csort, rank, B, s, sink, out_batch, &stop);
-        if (st) return st;
-        if (stop || k < nrec) return ST_E_FORMAT;
-    }
-    return n - rec.back() >= 8 ? ST_E_FORMAT : ST_OK;
+    return subset_section(SUBSET, h_in, n, S, csort, rank, &match, B, s, sink, out_batch);
 }
 
 // matched_section with one region: matched exactly as vcfc_dec::query_section
