@@ -229,13 +229,16 @@ def emu_hop_read(reset=True):
     return int(L.emu_hop_read(1 if reset else 0))
 
 
-def emu_line_index(vcf, S_hint=0, hop_walkers=0, learn=True, len_hint=0):
+def emu_line_index(vcf, S_hint=0, hop_walkers=0, learn=True, len_hint=0, cands=None, full=False):
     """The GPU line index of vcf (ending in '\n') on the emulator: (counts
     [lines, data lines, pass lines, long], data line offsets, lengths).
     hop_walkers: walkers of the hop index (0: the product's count); learn:
     the walkers with learned candidates (TRY / LEARN), else the GUESS ones
     (compress_device's choice for chr22-shaped files); len_hint: the GUESS
-    walkers' first line length (compress_device: the first data line's)."""
+    walkers' first line length (compress_device: the first data line's).
+    full: every table instead (emu_line_index_full; cands: its seeds)."""
+    if full or cands is not None:
+        return emu_line_index_full(vcf, S_hint, hop_walkers, learn, len_hint, cands)
     cap = vcf.count(b"\n") + 1
     off = np.zeros(cap, dtype=np.uint64)
     ln = np.zeros(cap, dtype=np.uint32)
@@ -248,6 +251,59 @@ def emu_line_index(vcf, S_hint=0, hop_walkers=0, learn=True, len_hint=0):
     assert st == 0
     k = int(cnt[1])
     return [int(c) for c in cnt], off[:k].tolist(), ln[:k].tolist()
+
+
+def emu_hop_steps(reset=True):
+    """The hop walkers' steps since the last reset, by name (the emulator's
+    VCFC_DIAG_HOP_STEP counters; names as line_index_cases.STEPS)."""
+    from line_index_cases import STEPS
+    L = lib()
+    out = (ctypes.c_ulonglong * 32)()
+    L.emu_hop_steps.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    k = L.emu_hop_steps(out, 1 if reset else 0)
+    assert k == len(STEPS)
+    return {name: int(out[i]) for i, name in enumerate(STEPS)}
+
+
+class _HopCands(ctypes.Structure):   # VcfcHopCands
+    _fields_ = [("g", ctypes.c_uint32 * 3), ("sig", (ctypes.c_uint16 * 16) * 3)]
+
+
+def emu_line_index_full(vcf, S_hint=0, hop_walkers=0, learn=True, len_hint=0, cands=None):
+    """The whole line index of vcf (ending in '\n') on the emulator, as
+    line_index_cases.plain_index states it: counts, the seven tables of
+    VcfcLineIndex and `ends` (phase 2's line ends in order).  cands: (g[3],
+    sig[3][16]), the learning walkers' seeds (VcfcHopCands), or None."""
+    cap = vcf.count(b"\n") + 1
+    u64 = lambda: np.zeros(cap, dtype=np.uint64)
+    u32 = lambda: np.zeros(cap, dtype=np.uint32)
+    t = dict(line_off=u64(), line_len=u32(), line_no=u32(), pass_off=u64(), pass_len=u32(), pass_no=u32(),
+             pass_before=u64(), ends=u64())
+    cnt = np.zeros(4, dtype=np.uint64)
+    hc = None
+    if cands is not None:
+        hc = _HopCands()
+        for k in range(3):
+            hc.g[k] = cands[0][k]
+            for j in range(16):
+                hc.sig[k][j] = cands[1][k][j]
+    L = lib()
+    vp = ctypes.c_void_p
+    L.emu_line_index_full.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int,
+                                      ctypes.c_uint32, vp, vp, ctypes.c_uint64] + [vp] * 8
+    st = L.emu_line_index_full(vcf, len(vcf), S_hint, hop_walkers, 1 if learn else 0, len_hint,
+                               ctypes.byref(hc) if hc is not None else None, cnt.ctypes.data, cap,
+                               *[t[k].ctypes.data for k in ("line_off", "line_len", "line_no", "pass_off", "pass_len",
+                                                            "pass_no", "pass_before", "ends")])
+    assert st == 0, st
+    c = [int(x) for x in cnt]
+    assert c[0] <= cap, c
+    out = {"counts": c, "ends": t["ends"][:c[0]].tolist()}
+    for k in ("line_off", "line_len", "line_no"):
+        out[k] = t[k][:c[1]].tolist()
+    for k in ("pass_off", "pass_len", "pass_no", "pass_before"):
+        out[k] = t[k][:c[2]].tolist()
+    return out
 
 
 def emu_synth_rows(n, samples, law, seed, row0=0, rows_of=None):

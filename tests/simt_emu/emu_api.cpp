@@ -10,6 +10,7 @@
 #include "vcfc_decode_driver.h"
 #include "emu.h"
 #include "host_buffers.h"
+#include "diag_retries.h"
 #include <atomic>
 
 // bytes the hop line index's walkers loaded (VCFC_DIAG_HOP_READ, diag_retries.h)
@@ -19,6 +20,17 @@ extern "C" unsigned long long emu_hop_read(int reset) {
     const unsigned long long v = g_hop_read.load();
     if (reset) g_hop_read = 0;
     return v;
+}
+
+// the hop walkers' steps by kind (VCFC_DIAG_HOP_STEP, diag_retries.h)
+static std::atomic<unsigned long long> g_hop_step[HOPSTEP_N];
+void emu_diag_hop_step(int what) { g_hop_step[what]++; }
+extern "C" int emu_hop_steps(unsigned long long *out, int reset) {
+    for (int i = 0; i < HOPSTEP_N; i++) {
+        out[i] = g_hop_step[i].load();
+        if (reset) g_hop_step[i] = 0;
+    }
+    return HOPSTEP_N;
 }
 
 static uint32_t g_last_deferred = 0;
@@ -256,7 +268,48 @@ extern "C" int emu_line_index(const uint8_t *in, uint64_t n, uint32_t S_hint, ui
     return 0;
 }
 
+// The same with every table of the index: `tab` = the seven tables in
+// VcfcLineIndex's order, each with room for cap entries, then the line ends
+// (phase 2's nl[], cap entries).  cands: the learning walkers' seeds or null.
+// The workspaces are poisoned: nothing may be read before it is written.
+extern "C" int emu_line_index_full(const uint8_t *in, uint64_t n, uint32_t S_hint, uint64_t hop_walkers, int learn,
+                                   uint32_t len_hint, const VcfcHopCands *cands, uint64_t *counts, uint64_t cap,
+                                   uint64_t *line_off, uint32_t *line_len, uint32_t *line_no, uint64_t *pass_off,
+                                   uint32_t *pass_len, uint32_t *pass_no, uint64_t *pass_before, uint64_t *ends) {
+    const VcfcLineIndexLayout L1 = vcfc_line_index_layout(n, 0);
+    std::vector<uint8_t> ws1(L1.total1 + 64, 0xCD);
+    std::vector<uint64_t> cnt(4, 0xCDCDCDCDCDCDCDCDull);
+    VcfcLineIndex x;
+    memset(&x, 0, sizeof x);
+    x.counts = cnt.data();
+    if (vcfc_line_index(in, n, ws1.data(), L1, x, nullptr, S_hint, hop_walkers, learn != 0, len_hint, cands) != hipSuccess)
+        return 1;
+    const uint64_t lines = cnt[0];
+    if (lines > n) return 2;
+    const VcfcLineIndexLayout L = vcfc_line_index_layout(n, lines);
+    std::vector<uint8_t> ws2(L.total2 + 64, 0xCD);
+    std::vector<uint64_t> lo(lines + 1), po(lines + 1), pb(lines + 1);
+    std::vector<uint32_t> ll(lines + 1), ln(lines + 1), pl(lines + 1), pn(lines + 1);
+    x.line_off = lo.data(); x.line_len = ll.data(); x.line_no = ln.data();
+    x.pass_off = po.data(); x.pass_len = pl.data(); x.pass_no = pn.data(); x.pass_before = pb.data();
+    if (vcfc_line_index_place(in, n, lines, ws1.data(), ws2.data(), L, x, nullptr) != hipSuccess) return 1;
+    memcpy(counts, cnt.data(), 32);
+    const uint64_t k = std::min<uint64_t>(lines, cap);
+    memcpy(line_off, lo.data(), 8 * k); memcpy(line_len, ll.data(), 4 * k); memcpy(line_no, ln.data(), 4 * k);
+    memcpy(pass_off, po.data(), 8 * k); memcpy(pass_len, pl.data(), 4 * k); memcpy(pass_no, pn.data(), 4 * k);
+    memcpy(pass_before, pb.data(), 8 * k);
+    memcpy(ends, ws2.data() + L.nl, 8 * k);
+    return 0;
+}
+
 // compress_device's choice of the hop index's learning (host code)
 extern "C" int emu_data_lines_irregular(const uint8_t *p, uint64_t len, uint32_t S) {
     return vcfc_ing::data_lines_irregular(p, len, S) ? 1 : 0;
+}
+// ... and of the walkers' first guess and first candidates
+extern "C" uint32_t emu_first_data_line_len(const uint8_t *p, uint64_t len) {
+    return vcfc_ing::first_data_line_len(p, len);
+}
+extern "C" void emu_learn_candidates(const uint8_t *p, uint64_t len, uint32_t S, VcfcHopCands *c) {
+    vcfc_ing::learn_candidates(p, len, S, c);
 }

@@ -144,7 +144,7 @@ def test_line_longer_than_max_chunk():
 
 
 def test_short_lines_overflow_the_segment_slot():
-    """More than 256 lines in a 16 KiB segment of the line index (short '##'
+    """More than 128 (NL_SLOT) lines in a 16 KiB segment of the line index (short '##'
     lines, runs of empty lines): those segments are scanned again."""
     rnd = random.Random(11)
     head = b"".join(b"##k%d=%d\n" % (i, rnd.randrange(10)) for i in range(4000))

@@ -41,6 +41,15 @@
 #ifndef VCFC_DIAG_HOP_READ
 #define VCFC_DIAG_HOP_READ(bytes)   // bytes a walker loads in one round (emulator diagnostics)
 #endif
+#ifndef VCFC_DIAG_HOP_STEP
+// a walker's step (emulator diagnostics): LINE_FIRST (LINE: the end in the
+// first window), LINE_CHECK (the predicted end checked in LINE's own round),
+// VERIFY_HIT / VERIFY_MISS, FIND (an end found by FIND), TRY_HIT / TRY_MISS
+// (a learned candidate held / none did), LEARN (a candidate inserted),
+// GUESS_TAKEN / GUESS_FAIL (a guessed line taken / the window that failed),
+// TRUST_ZERO (the walker stops trying)
+#define VCFC_DIAG_HOP_STEP(what)
+#endif
 
 namespace {
 
@@ -371,6 +380,7 @@ __global__ __launch_bounds__(256) void k_nl_hop(const uint8_t *buf, uint64_t n, 
             const uint64_t e = ws + jf;
             if (go) {
                 if (!hit || e <= s) {   // the guess failed: this line by LINE
+                    if (l == w0) VCFC_DIAG_HOP_STEP(GUESS_FAIL);
                     nextm = HOP_LINE;
                     go = false;
                 } else if (e >= hi) {
@@ -379,6 +389,7 @@ __global__ __launch_bounds__(256) void k_nl_hop(const uint8_t *buf, uint64_t n, 
                 } else {
                     // (the next line's kind, when its first byte is in the window)
                     record(e, jn < GW ? (nb == '\n' ? 1u : nb == '#' ? 3u : 2u) : 0u);
+                    if (l == w0) VCFC_DIAG_HOP_STEP(GUESS_TAKEN);
                     s = e + 1;
                     gn++;
                     // the next line: past the span, its first byte not in
@@ -467,6 +478,7 @@ __global__ __launch_bounds__(256) void k_nl_hop(const uint8_t *buf, uint64_t n, 
             if (first != ~0ull) { e = first; found = true; }
             else if (q + 1024 >= n) { e = n - 1; found = true; }   // (buf[n - 1] is '\n')
             else q += 1024;
+            if (l == w0 && found) VCFC_DIAG_HOP_STEP(FIND);
             // a data line the candidates did not know: learn its region
             if (LEARN && found && lrn && trust && e >= gt + GW - 1) { found = false; mode = HOP_LEARN; }
         }
@@ -503,6 +515,8 @@ __global__ __launch_bounds__(256) void k_nl_hop(const uint8_t *buf, uint64_t n, 
                 const uint32_t sw0 = (uint32_t)__builtin_ctzll(lm) & ~15u;
                 const uint32_t Gown = (uint32_t)(e - gt);
                 const uint32_t Gs = vw::shfl(Gown, sw0), ss = vw::shfl(gtm, sw0 + wl);
+                if (l == w0 && mode0 == HOP_LEARN && gv && Gown != cg[0] && Gown != cg[1] && Gown != cg[2])
+                    VCFC_DIAG_HOP_STEP(LEARN);   // (a length not yet held: one of the inserts below takes it)
                 insert(Gs, ss);
                 if (mode0 == HOP_LEARN && gv) insert(Gown, gtm);
             }
@@ -530,8 +544,11 @@ __global__ __launch_bounds__(256) void k_nl_hop(const uint8_t *buf, uint64_t n, 
         const uint32_t b0 = vw::shfl(v[0].x & 0xFFu, w0);
         if (mode == HOP_LINE) {
             lrn = false;
-            if (first != ~0ull) { e = first; found = true; }
-            else if (S == 0 || b0 == '#') { mode = HOP_FIND; q = p + 256u * rows; }
+            if (first != ~0ull) {
+                e = first;
+                found = true;
+                if (l == w0) VCFC_DIAG_HOP_STEP(LINE_FIRST);
+            } else if (S == 0 || b0 == '#') { mode = HOP_FIND; q = p + 256u * rows; }
             else if (t9 == ~0u) {
                 if (rows < 4) rows = 4;                              // the line again with 1 KiB
                 else { mode = HOP_FIND; q = p + 1024; }
@@ -552,7 +569,10 @@ __global__ __launch_bounds__(256) void k_nl_hop(const uint8_t *buf, uint64_t n, 
             }
         } else if (mode == HOP_VERIFY) {
             if (gv && e >= g0 + 124) check = true;
-            else to_try(p);
+            else {
+                if (l == w0) VCFC_DIAG_HOP_STEP(VERIFY_MISS);
+                to_try(p);
+            }
         } else if (mode == HOP_TRY && tdef && gv) {
             check = true;
         }
@@ -570,6 +590,9 @@ __global__ __launch_bounds__(256) void k_nl_hop(const uint8_t *buf, uint64_t n, 
         }
         const bool bw = wbits(bad) != 0;
         if (check) {
+            if (l == w0 && mode0 == HOP_LINE && !bw) VCFC_DIAG_HOP_STEP(LINE_CHECK);
+            if (l == w0 && mode0 == HOP_VERIFY && !bw) VCFC_DIAG_HOP_STEP(VERIFY_HIT);
+            if (l == w0 && mode0 == HOP_VERIFY && bw) VCFC_DIAG_HOP_STEP(VERIFY_MISS);
             if (!bw) found = true;
             else if (mode0 != HOP_TRY) to_try(p + 256u * nr);   // (past the first window: no '\n' there)
         }
@@ -578,8 +601,11 @@ __global__ __launch_bounds__(256) void k_nl_hop(const uint8_t *buf, uint64_t n, 
                 e = gt + chit;
                 found = true;
                 trust = trust < HOP_TRUST ? trust + 1 : trust;
+                if (l == w0) VCFC_DIAG_HOP_STEP(TRY_HIT);
             } else {
                 mode = HOP_FIND;   // (q: where the prediction left it)
+                if (l == w0) VCFC_DIAG_HOP_STEP(TRY_MISS);
+                if (l == w0 && trust == 1) VCFC_DIAG_HOP_STEP(TRUST_ZERO);
                 trust = trust ? trust - 1 : 0;
             }
         }
