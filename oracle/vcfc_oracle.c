@@ -453,10 +453,12 @@ int vcfo_sparsify(const uint8_t *in, size_t n, const char *out_path) {
         if (c2 == '#') got_meta = 1; else { if (!got_meta) { close(fd); return VCFO_E_FORMAT; } got_header = 1; }
         const uint8_t *nl = memchr(in + ip + 2, '\n', n - ip - 2);
         if (!nl) { close(fd); return VCFO_E_FORMAT; }
-        size_t e = (size_t)(nl - in) + 1;
-        if (write(fd, in + ip, e - ip) != (ssize_t)(e - ip)) { close(fd); return VCFO_E_IO; }
-        ip = e;
+        ip = (size_t)(nl - in) + 1;
     }
+    /* the header lines are written only once all of them are read (:330-335):
+     * a throw among them, the end of the file behind the last one included,
+     * leaves the output created and empty */
+    if (write(fd, in, ip) != (ssize_t)ip) { close(fd); return VCFO_E_IO; }
     uint8_t zero8[8] = {0};
     if (write(fd, zero8, 8) != 8) { close(fd); return VCFO_E_IO; }
     uint64_t data_start = (uint64_t)lseek(fd, 0, SEEK_CUR);

@@ -150,14 +150,15 @@ def emu_encode(buf, line_off, line_len, cap=None, total=None):
     return st, out[:total].tobytes(), rec_off, err.value
 
 
-def emu_sparse_plan(recs, rec_off, data_start):
-    """Run k_sparse_plan on the emulator: (file_off, prefix16 bytes, status[2])."""
+def emu_sparse_plan(recs, rec_off, data_start, fill=0):
+    """Run k_sparse_plan on the emulator: (file_off, prefix16 bytes, status[2]);
+    the outputs start out as bytes of `fill`."""
     n = len(rec_off) - 1
     src = np.frombuffer(recs, dtype=np.uint8).copy()
     ro = np.ascontiguousarray(rec_off, dtype=np.uint64)
-    fo = np.zeros(max(n, 1), dtype=np.uint64)
-    pf = np.zeros(16 * max(n, 1), dtype=np.uint8)
-    stt = np.zeros(2, dtype=np.uint64)
+    fo = np.full(8 * max(n, 1), fill, dtype=np.uint8).view(np.uint64)
+    pf = np.full(16 * max(n, 1), fill, dtype=np.uint8)
+    stt = np.full(16, fill, dtype=np.uint8).view(np.uint64)
     lib().emu_sparse_plan(src.ctypes.data, ro.ctypes.data, n, data_start, fo.ctypes.data, pf.ctypes.data,
                           stt.ctypes.data)
     return fo[:n], pf[:16 * n].tobytes(), stt

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import golden_io as G
+import sparse_cases as C
 
 pytestmark = pytest.mark.gpu
 REPO = G.REPO
@@ -96,3 +97,37 @@ def test_chr22_shaped_2504_samples(ctx):
         for q in (b"22:%d-%d" % (pos[7] + 1, pos[9]), b"22:1-%d" % pos[3], b"21:%d-%d" % (pos[0], pos[50]),
                   b"22:%d-%d" % (pos[n - 1] + 5, pos[n - 1] + 9)):
             assert ctx.sparse_query_status(sp, q) == G.oracle_sparse_query(sp, q), q
+
+
+@pytest.mark.parametrize("seed", [1, 2, 3, 4])
+def test_mutated_files(ctx, seed):
+    """The GPU twin of test_sparse_emu.test_sparse_query_driver_on_mutated_files:
+    the same random byte patches (sparse_cases.mutate_random_sparse) in a file
+    written by this build's sparsify, against the oracle restatement."""
+    d = G.sparse_query_cases()
+    with tempfile.TemporaryDirectory(dir="/tmp") as wd:
+        path = os.path.join(wd, "m.sparse")
+        G.build_sparse_file(d, "random_100x10000", path, gpu_sparsify(ctx, wd))
+        C.mutate_random_sparse(path, seed)
+        for q in C.MUTATED_QUERIES:
+            got = ctx.sparse_query_status(path, q)
+            want = G.oracle_sparse_query(path, q)
+            assert got == want, (seed, q, got[0], want[0], len(got[1]), len(want[1]))
+
+
+def test_adjacent_files(ctx):
+    """Queries at every record's POS and over the whole span of the adjacent
+    files of sparse_cases.py (records that end at, one byte short of and one
+    byte into the next record's slot, duplicate and decreasing POS, a record
+    over two slots), sparsified by this build: later writes win."""
+    with tempfile.TemporaryDirectory(dir="/tmp") as wd:
+        outcomes = set()
+        for name, v in C.adjacent():
+            path = os.path.join(wd, name + ".sparse")
+            gpu_sparsify(ctx, wd)(v, path)
+            for q in C.span_queries(v):
+                got = ctx.sparse_query_status(path, q)
+                want = G.oracle_sparse_query(path, q)
+                assert got == want, (name, q, got[0], want[0], len(got[1]), len(want[1]))
+                outcomes.add((want[0], bool(want[1])))
+        assert {(0, True), (8, False)} <= outcomes

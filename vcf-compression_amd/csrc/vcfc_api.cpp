@@ -133,15 +133,17 @@ int parse_vcfc_header(const uint8_t *in, uint64_t n, uint64_t *data_off, uint64_
 
 // Record starts by hopping the LEN headers (read_compressed_line_length_headers,
 // src/compress.cpp:270-331; both headers must carry extension count 3,
-// src/utils.hpp:198-206).  rec[i] = offset of record i from `base`, rec[n] = end.
+// src/utils.hpp:198-206).  rec[i] = offset of record i from `base`, rec[n] = end
+// of the last whole record -- also where a bad header stops the walk, so the
+// records before it are all indexed.
 int index_records(const uint8_t *base, uint64_t n, std::vector<uint64_t> &rec) {
     rec.clear();
     uint64_t ip = 0;
     while (n - ip >= 8) {
         const uint8_t *h = base + ip;
-        if ((h[0] >> 6) != 3 || (h[4] >> 6) != 3) return VCFC_E_FORMAT;
+        if ((h[0] >> 6) != 3 || (h[4] >> 6) != 3) break;
         const uint32_t L = ((uint32_t)(h[0] & 0x3F) << 24) | ((uint32_t)h[1] << 16) | ((uint32_t)h[2] << 8) | h[3];
-        if (L < 4 || n - ip - 8 < (uint64_t)L - 4) return VCFC_E_FORMAT;
+        if (L < 4 || n - ip - 8 < (uint64_t)L - 4) break;
         rec.push_back(ip);
         ip += 8 + (L - 4);
     }
@@ -648,7 +650,15 @@ int vcfc_sparsify_file(vcfc_ctx *c, const char *in_path, const char *out_path) {
     if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
     SparseInput in;
     int st = in.open(in_path);
-    if (st) return st;
+    if (st) {
+        // the reference creates the output once the input is open and throws on
+        // a bad header before it writes a byte: the output is left empty
+        if (in.f.fd >= 0) {
+            const int fd = open(out_path, O_CREAT | O_TRUNC | O_RDWR, 0600);
+            if (fd >= 0) close(fd);
+        }
+        return st;
+    }
     const uint64_t n = in.n;
     std::vector<uint64_t> file_off;
     std::vector<uint8_t> prefix;

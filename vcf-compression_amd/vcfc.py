@@ -1112,6 +1112,14 @@ def record_hash_device(d_recs, d_rec_off, n, d_hash, stream=0):
     raise_for(lib().vcfc_record_hash_device(d_recs, d_rec_off, n, d_hash, stream))
 
 
+def sparse_plan_device(d_recs, d_rec_off, n, data_start, d_file_off, d_prefix16, d_status, stream=0):
+    """The sparse layout of device-resident records (include/vcfc.h
+    vcfc_sparse_plan_device): file offsets, 16-byte prefixes and the two
+    status words, enqueued on `stream`."""
+    raise_for(lib().vcfc_sparse_plan_device(d_recs, d_rec_off, n, data_start, d_file_off, d_prefix16, d_status,
+                                            stream))
+
+
 def sparse_index_workspace_size(n_records):
     return int(_need("vcfc_sparse_index_workspace_size")(n_records))
 
