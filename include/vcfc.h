@@ -417,7 +417,13 @@ int vcfc_query_sparse_index_file(vcfc_ctx *ctx, const char *in_vcfc, const char 
  * required columns and each sample-section byte read, the closing LF counted
  * only where it ends an uncompressed column.  The last three may all be
  * null.  d_err: ~0 or (i << 8 | code) of the first record the decoder
- * refuses (its codes 2, 3); entries from record i on are undefined. */
+ * refuses (its codes 2, 3); entries from record i on are undefined.
+ *
+ * One deviation: a record whose POS text does not lie wholly in its required
+ * columns -- fewer than two non-empty fields there, or the second one ended
+ * by the columns' end with sample tokens after it -- is refused (code 3),
+ * where the reference prints the field as it runs on into the sample tokens;
+ * no file written by compress has such a record. */
 uint64_t vcfc_decode_sizes_workspace_size(uint64_t n_records);
 int vcfc_decode_sizes_device(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_rec_start, uint64_t n,
                              uint64_t sample_count, uint64_t *d_line_off, uint64_t *d_pos_off, uint32_t *d_pos_len,

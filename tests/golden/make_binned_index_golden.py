@@ -4,7 +4,12 @@ and `main query-binned-index <file.vcfc> <region>` (oracle/_ref/main, compiled
 from the reference's sources by oracle/Makefile), over the committed
 random_100x10000 fixture, a small seeded file of edge records and three files
 the reference throws on.  Run where the reference build exists; writes
-binned_index_cases.json (data only)."""
+binned_index_cases.json (data only).
+
+edge_cases(): the same two actions over the hand-built edge files of
+tests/index_edge_cases.py whose records all hold their TABs (pinned_files());
+make_sparse_index_golden.py --edge records them, with its own, into
+index_edge_cases.json."""
 import hashlib
 import json
 import os
@@ -195,6 +200,35 @@ def main():
           sorted(backed))
     for (name, b), idx in sorted(indexes.items()):
         print(name, b, len(idx) // 13, "entries")
+
+
+EDGE_BINS = [1, 2, 64]
+
+
+def edge_cases(wd, files, queries):
+    """(index cases, query cases) of the reference over `files` {name: .vcfc
+    bytes}: the index at bins 1, 2 and 64 as its length and digest, and for
+    queries[name] = (bin, regions) the stdout of each region against the
+    reference's own index."""
+    index_cases, query_cases = [], []
+    path = os.path.join(wd, "e.vcfc")
+    for name, data in files.items():
+        with open(path, "wb") as f:
+            f.write(data)
+        for b in EDGE_BINS:
+            if os.path.exists(path + ".vcfci"):
+                os.unlink(path + ".vcfci")
+            rc, out = run(["create-binned-index", str(b), path], wd)
+            idx = open(path + ".vcfci", "rb").read() if os.path.exists(path + ".vcfci") else b""
+            index_cases.append({"file": name, "bin": b, "rc": rc, "index_len": len(idx),
+                                "index_sha256": hashlib.sha256(idx).hexdigest()})
+            if name in queries and queries[name][0] == b:
+                assert rc == 0 and len(idx) // 13 >= 2, (name, b, rc)
+                for region in queries[name][1]:
+                    rc, out = run(["query-binned-index", path, region], wd)
+                    query_cases.append({"file": name, "bin": b, "region": region, "rc": rc, "stdout_len": len(out),
+                                        "stdout_sha256": hashlib.sha256(out).hexdigest()})
+    return index_cases, query_cases
 
 
 if __name__ == "__main__":

@@ -5,7 +5,12 @@
 the reference's sources by oracle/Makefile).  An index is recorded as its
 apparent size and the (offset, 13 bytes) of its non-zero slots, read through
 SEEK_DATA / SEEK_HOLE.  Run where the reference build exists, on a file
-system with sparse files; writes sparse_index_cases.json (data only)."""
+system with sparse files; writes sparse_index_cases.json (data only).
+
+--edge: instead, the three actions (and make_binned_index_golden.edge_cases)
+over the hand-built edge files of tests/index_edge_cases.py whose records all
+hold their TABs, recorded as lengths, digests and exit codes with the digest
+of each input file into index_edge_cases.json (data only)."""
 import hashlib
 import json
 import os
@@ -153,5 +158,45 @@ def main():
         print(q["file"], q["region"], q["rc"], q["stdout_len"], repr(q.get("stderr", ""))[:60])
 
 
+def edge_main():
+    import index_edge_cases as EC
+    if not os.path.exists(REF_MAIN):
+        sys.exit("build the reference first: make -C oracle")
+    files = EC.pinned_files()
+    create_cases, gap_cases, query_cases = [], [], []
+    with tempfile.TemporaryDirectory(dir=os.environ.get("SPARSE_GOLDEN_TMP")) as wd:
+        index_cases, binned_query_cases = MB.edge_cases(wd, files, EC.PINNED_BINNED_QUERIES)
+        path = os.path.join(wd, "f.vcfc")
+        index = path + ".vcfci-sparse"
+        sp = os.path.join(wd, "start-positions.txt")
+        for name, data in files.items():
+            with open(path, "wb") as f:
+                f.write(data)
+            for p in (index, sp):
+                if os.path.exists(p):
+                    os.unlink(p)
+            rc, out, err = run(["create-sparse-index", path], wd)
+            slots, size = SX.read_sparse_file(index)
+            create_cases.append({"file": name, "rc": rc, "size": size, "n_slots": len(slots),
+                                 "slots_sha256": SX.slots_digest(slots), "seek_failed": int(b"lseek" in err)})
+            for region in EC.PINNED_SPARSE_QUERIES.get(name, ()):
+                rc, out, err = run(["query-sparse-index", path, region], wd)
+                query_cases.append({"file": name, "region": region, "rc": rc, "stdout_len": len(out),
+                                    "stdout_sha256": hashlib.sha256(out).hexdigest()})
+            if name in EC.PINNED_NO_GAP:
+                continue
+            rc, out, _ = run(["gap-analysis", path], wd)
+            txt = open(sp, "rb").read() if os.path.exists(sp) else b""
+            gap_cases.append({"file": name, "rc": rc, "txt_len": len(txt), "txt_sha256": hashlib.sha256(txt).hexdigest()})
+    meta = {k: {"len": len(v), "sha256": hashlib.sha256(v).hexdigest()} for k, v in files.items()}
+    with open(os.path.join(HERE, "index_edge_cases.json"), "w") as f:
+        json.dump({"generator": "tests/golden/make_sparse_index_golden.py --edge (reference: oracle/_ref/main)",
+                   "files": meta, "index_cases": index_cases, "binned_query_cases": binned_query_cases,
+                   "create_cases": create_cases, "sparse_query_cases": query_cases, "gap_cases": gap_cases}, f,
+                  separators=(",", ":"))
+    print(len(files), "files,", len(index_cases), "index cases,", len(create_cases), "create cases,", len(gap_cases),
+          "gap cases,", len(binned_query_cases) + len(query_cases), "query cases")
+
+
 if __name__ == "__main__":
-    main()
+    edge_main() if "--edge" in sys.argv[1:] else main()

@@ -3,9 +3,12 @@ src/main.cpp:1284-1637, and query_binned_index_binarysearch, :2974-3349):
 byte-exact against the reference CLI's recorded index files, stdout and exit
 codes (tests/golden/binned_index_cases.json) through the C ABI (libvcfc.so)
 and the CLI (build/main), the device entry points on freshly encoded batches
-against the restatement (index_cases.py), and the indexed query against the
-full-scan query at 2504 samples.  Valid inputs only: malformed files run on
-the emulator (test_index_emu.py)."""
+against the restatement (index_cases.py), the indexed query against the
+full-scan query at 2504 samples, and the hand-built edge families of
+index_edge_cases.py -- records compress would not write, both error codes,
+the error word's order, a short entries_cap, ends at and above 2^32 -- with
+the odd-field and mutated-file cases, uploaded as they stand: the same checks
+test_index_emu.py runs on the emulator."""
 import io
 import os
 import subprocess
@@ -17,6 +20,7 @@ import pytest
 
 import golden_io as G
 import index_cases as X
+import index_edge_cases as EC
 
 pytestmark = pytest.mark.gpu
 REPO = G.REPO
@@ -241,3 +245,79 @@ def test_index_2504x4000(ctx):
         st, got = ctx.query_binned_index_status(enc, idx, q)
         st_f, full = ctx.query_buffer(enc, q)
         assert st == OK and st_f == OK and got == full == b"".join(l + b"\n" for l in lines[a:b + 1]), (a, b)
+
+
+# ---- the hand-built edge families (index_edge_cases.py) on the GPU -------------------
+
+def u64(t):
+    return t.cpu().numpy().view(np.uint64).tolist()
+
+
+@pytest.fixture(scope="module")
+def gpu(ctx):
+    """The callables index_edge_cases.py checks: the device entry points on
+    the uploaded records, create and query through the C ABI."""
+    import torch
+    import vcfc
+    dev = "cuda:0"
+
+    def span(v):
+        d, rec, n, h, _ = EC.upload(v)
+        ref = torch.empty(n, dtype=torch.uint8, device=dev)
+        pos = torch.empty(n, dtype=torch.int64, device=dev)
+        end = torch.empty(n, dtype=torch.int64, device=dev)
+        err = torch.empty(1, dtype=torch.int64, device=dev)
+        vcfc.record_span_device(d.data_ptr(), rec.data_ptr(), n, ref.data_ptr(), pos.data_ptr(), end.data_ptr(),
+                                err.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        return u64(err)[0], ref.cpu().tolist(), u64(pos), u64(end)
+
+    def device(v, E, cap):
+        d, rec, n, h, _ = EC.upload(v)
+        cap = n if cap is None else cap
+        ent = torch.full((13 * cap + 16,), 0xEE, dtype=torch.uint8, device=dev)
+        words = torch.empty(2, dtype=torch.int64, device=dev)   # count, largest end
+        err = torch.empty(1, dtype=torch.int64, device=dev)
+        wsb = vcfc.index_workspace_size(n)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        vcfc.binned_index_device(d.data_ptr(), rec.data_ptr(), n, h, E, ent.data_ptr(), cap, words.data_ptr(),
+                                 words.data_ptr() + 8, ws.data_ptr(), wsb, err.data_ptr(),
+                                 torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        w, got = u64(words), ent.cpu().numpy()
+        used = min(w[0], cap)
+        if u64(err)[0] == NO_ERROR or u64(err)[0] & 0xFF == 0xFF:
+            assert (got[13 * used:] == 0xEE).all(), "entries written past the count or entries_cap"
+        assert (got[13 * cap:] == 0xEE).all(), "entries written past entries_cap"
+        return [u64(err)[0], w[0], w[1]], got[:13 * used].tobytes()
+
+    class B:
+        pass
+    B.span, B.device = staticmethod(span), staticmethod(device)
+    B.create = staticmethod(lambda v, E: ctx.create_binned_index_status(v, E))
+    B.query = staticmethod(lambda v, idx, q, **kw: ctx.query_binned_index_status(v, idx, q))
+    return B
+
+
+@pytest.mark.parametrize("family", sorted(EC.BINNED))
+def test_edge_family(gpu, family):
+    EC.BINNED[family](gpu)
+
+
+@pytest.mark.parametrize("n", EC.NS)
+def test_edge_prefix_max(gpu, n):
+    EC.binned_prefix_max(gpu, n)
+
+
+def test_edge_prefix_max_second_trip(gpu):
+    """65 836 records: 258 block maxima, so k_idx_partials takes its second trip."""
+    EC.binned_prefix_max_second_trip(gpu)
+
+
+def test_odd_fields(gpu):
+    EC.check_odd_fields(gpu)
+
+
+@pytest.mark.parametrize("seed", EC.MUTATE_SEEDS)
+def test_mutated_files(gpu, seed):
+    EC.check_mutated_binned(gpu, seed)

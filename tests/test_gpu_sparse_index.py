@@ -4,9 +4,12 @@ query_sparse_external_index, :1002-1281) and gap-analysis (:3931-3980):
 against the reference CLI's recorded index contents, stdout, stderr and exit
 codes (tests/golden/sparse_index_cases.json) through the C ABI (libvcfc.so)
 and the CLI (build/main), the device entry points on freshly encoded batches
-against the restatement (sparse_index_cases.py), and one 2504-sample file
-against the VCF's own lines.  Malformed files beyond the golden ones run on
-the emulator (test_sparse_index_emu.py)."""
+against the restatement (sparse_index_cases.py), one 2504-sample file
+against the VCF's own lines, and the hand-built edge families of
+index_edge_cases.py -- records compress would not write, both error codes,
+the error word's order, status[1] and status[2], the gap fields -- with the
+short / structural, unsorted and mutated-file cases, uploaded as they stand:
+the same checks test_sparse_index_emu.py runs on the emulator."""
 import io
 import os
 import subprocess
@@ -18,6 +21,7 @@ import pytest
 
 import golden_io as G
 import index_cases as X
+import index_edge_cases as EC
 import sparse_index_cases as SX
 
 pytestmark = pytest.mark.gpu
@@ -293,3 +297,106 @@ def test_sparse_index_2504x4000(ctx, wd):
         assert pos == dl[i].split(b"\t")[1] and int(size_) == len(dl[i]) + 1, i
         assert int(cnt) == SX.compressed_count(enc[p:p + k], 2504), i
         p += k
+
+
+# ---- the hand-built edge families (index_edge_cases.py) on the GPU -------------------
+
+def u64(t):
+    return t.cpu().numpy().view(np.uint64).tolist()
+
+
+@pytest.fixture(scope="module")
+def gpu(ctx, wd):
+    """The callables index_edge_cases.py checks: the device entry points on
+    the uploaded records; create, query and gap-analysis through the C ABI's
+    file entries."""
+    import torch
+    import vcfc
+    dev = "cuda:0"
+    path = os.path.join(wd, "edge.vcfc")
+
+    def put_file(v):
+        with open(path, "wb") as f:
+            f.write(v)
+
+    def device(v):
+        d, rec, n, h, _ = EC.upload(v)
+        wsb = vcfc.sparse_index_workspace_size(n)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        ent = torch.full((13 * n + 16,), 0xEE, dtype=torch.uint8, device=dev)
+        fo = torch.full((n + 2,), -1, dtype=torch.int64, device=dev)
+        words = torch.empty(4, dtype=torch.int64, device=dev)   # count, status[0..2]
+        err = torch.empty(1, dtype=torch.int64, device=dev)
+        vcfc.sparse_index_device(d.data_ptr(), rec.data_ptr(), n, h, ent.data_ptr(), fo.data_ptr(), words.data_ptr(),
+                                 words.data_ptr() + 8, ws.data_ptr(), wsb, err.data_ptr(),
+                                 torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        w, got_e, got_o = u64(words), ent.cpu().numpy(), u64(fo)
+        cnt = w[0]
+        assert cnt <= n and (got_e[13 * cnt:] == 0xEE).all() and all(o == NO_ERROR for o in got_o[cnt:])
+        return [u64(err)[0]] + w, got_e[:13 * cnt].tobytes(), got_o[:cnt]
+
+    def create(v):
+        put_file(v)
+        st, bad, sf = ctx.create_sparse_index_status(path)
+        slots, size = SX.read_sparse_file(path + ".vcfci-sparse")
+        return st, slots, bad, sf, size
+
+    def query(v, slots, q, **kw):
+        put_file(v)
+        SX.write_sparse_file(path + ".vcfci-sparse", slots)
+        return query_abi(ctx, path, q, wd)
+
+    def gap(v):
+        put_file(v)
+        txt = os.path.join(wd, "edge_gap.txt")
+        if os.path.exists(txt):
+            os.unlink(txt)
+        try:
+            ctx.gap_analysis(path, txt)
+            st = OK
+        except RuntimeError:
+            st = E_FORMAT
+        if not os.path.exists(txt):
+            return st, b"", None
+        with open(txt, "rb") as f:
+            return st, f.read(), None
+
+    def sizes(v, S):
+        d, rec, n, h, nbytes = EC.upload(v)
+        wsb = vcfc.decode_sizes_workspace_size(n)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        loff = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        po = torch.zeros(n, dtype=torch.int64, device=dev)
+        pl = torch.zeros(n, dtype=torch.int32, device=dev)
+        cc = torch.zeros(n, dtype=torch.int64, device=dev)
+        err = torch.empty(1, dtype=torch.int64, device=dev)
+        vcfc.decode_sizes_device(d.data_ptr(), nbytes, rec.data_ptr(), n, S, loff.data_ptr(), po.data_ptr(),
+                                 pl.data_ptr(), cc.data_ptr(), ws.data_ptr(), wsb, err.data_ptr(),
+                                 torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        return u64(err)[0], loff.cpu().tolist(), po.cpu().tolist(), pl.cpu().tolist(), cc.cpu().tolist()
+
+    class B:
+        pass
+    B.device, B.create, B.query = staticmethod(device), staticmethod(create), staticmethod(query)
+    B.gap, B.sizes = staticmethod(gap), staticmethod(sizes)
+    return B
+
+
+@pytest.mark.parametrize("family", sorted(EC.SPARSE))
+def test_edge_family(gpu, family):
+    EC.SPARSE[family](gpu)
+
+
+def test_short_and_structural_records(gpu):
+    EC.check_short_and_structural(gpu)
+
+
+def test_unsorted_falls_back_to_record_order(gpu):
+    EC.check_unsorted(gpu)
+
+
+@pytest.mark.parametrize("seed", EC.MUTATE_SEEDS)
+def test_mutated_files(gpu, seed):
+    EC.check_mutated_sparse(gpu, seed)

@@ -2,8 +2,9 @@
 against the reference CLI's recorded results
 (tests/golden/binned_index_cases.json), then the product kernels
 (csrc/vcfc_index.hip) and host drivers (csrc/vcfc_index_driver.h) compiled
-against the fiber SIMT emulator, against the goldens and the restatement.
-test_gpu_index.py repeats the valid-input part on the GPU."""
+against the fiber SIMT emulator, against the goldens and the restatement, and
+the hand-built edge families of index_edge_cases.py.  test_gpu_index.py
+repeats the generated inputs and the edge families on the GPU."""
 import ctypes
 import random
 
@@ -13,6 +14,7 @@ import pytest
 import emu_io
 import golden_io as G
 import index_cases as X
+import index_edge_cases as EC
 
 OK, E_ARG, E_FORMAT = 0, 5, 8
 NO_ERROR = (1 << 64) - 1
@@ -192,27 +194,30 @@ def test_emu_end_past_2_32_replays_on_the_host():
     assert differ   # the parallel form alone would be wrong here
 
 
+def test_restatement_matches_reference_edge_cases():
+    EC.check_pinned_binned()
+
+
+class EMU:
+    """The callables index_edge_cases.py checks, on the emulator."""
+    span = staticmethod(emu_span)
+    device = staticmethod(lambda v, E, cap: emu_device(v, E, cap))
+    create = staticmethod(emu_create)
+    query = staticmethod(emu_query)
+
+
 def test_emu_odd_fields():
-    """Fields the generator does not draw: negative and overflowing POS,
-    END lists with signs and blanks, '=' runs, duplicate keys, an ALT of commas only."""
-    rows = [b"1\t 7\t.\tACG\tA\t1\tPASS\t.", b"1\t-3\t.\tA\tC\t1\tPASS\t.", b"1\t99999999999999999999\t.\tA\tC\t1\tPASS\t.",
-            b"1\t50\t.\tA\t<X>\t1\tPASS\tEND=-5, 70,+60", b"1\t50\t.\tA\t<X>\t1\tPASS\tEND=", b"1\t50\t.\tA\t<X>\t1\tPASS\tEND",
-            b"1\t50\t.\tA\t<X>\t1\tPASS\t=END=9;END=8", b"1\t50\t.\tA\t<X>\t1\tPASS\tSVLEN=-9223372036854775808,4",
-            b"1\t50\t.\tA\tC<\t1\tPASS\tSVLEN=18446744073709551615",
-            b"22\t0\t.\tA\t,\t1\tPASS\t.", b"M\t5\t" + b"i" * 70 + b"\tA\tCC\t1\tPASS\t.", b"23\t5\t.\tA\tC\t1\tPASS\t."]
-    vcf = X.header(1) + b"".join(r + b"\tGT\t0|1\n" for r in rows)
-    st, v, _ = G.oracle_compress(vcf)
-    assert st == 0
-    sp, bad = X.spans_of(v)
-    assert bad is None
-    err, ref, pos, end = emu_span(v)
-    assert err == NO_ERROR
-    assert (ref, pos, end) == ([s[1] for s in sp], [s[2] for s in sp], [s[3] for s in sp])
-    for E in (1, 2):
-        assert emu_create(v, E) == X.build_index(v, E)
-    for bad_info in (b"END=1;=", b"A=B=C", b"END=1x", b"SVLEN=3,x"):
-        st, w, _ = G.oracle_compress(vcf + b"1\t60\t.\tA\t<X>\t1\tPASS\t" + bad_info + b"\tGT\t0|1\n")
-        assert emu_create(w, 1) == (E_FORMAT, b"", len(rows)) == X.build_index(w, 1), bad_info
+    EC.check_odd_fields(EMU)
+
+
+@pytest.mark.parametrize("family", sorted(EC.BINNED))
+def test_emu_edge_family(family):
+    EC.BINNED[family](EMU)
+
+
+@pytest.mark.parametrize("n", EC.NS)
+def test_emu_edge_prefix_max(n):
+    EC.binned_prefix_max(EMU, n)
 
 
 def test_emu_index_edge_rules():
@@ -231,36 +236,14 @@ def test_emu_index_edge_rules():
     assert emu_query(v, X.pack([(1, 0, 2), (1, 0, 2)]), "1:100-200")[0] == E_FORMAT   # inside the header
 
 
-def mutate(v, rnd, patches):
-    """Random byte patches in record headers (LEN, REQ) and prefixes (CHROM .. INFO)."""
-    b = bytearray(v)
-    h, ro = rec_offsets(v)
-    for _ in range(patches):
-        r = rnd.randrange(len(ro) - 1)
-        p = h + ro[r] + rnd.choice([rnd.randrange(0, 8), rnd.randrange(8, 60)])
-        if p < len(b):
-            b[p] = rnd.choice([rnd.randrange(256), 9, 0x3C, 0x3D, 0x3B, 0x2C, 0x30])
-    return bytes(b)
-
-
-@pytest.mark.parametrize("seed", [1, 2, 3, 4])
+@pytest.mark.parametrize("seed", EC.MUTATE_SEEDS)
 def test_emu_mutated_files(seed):
-    rnd = random.Random(seed)
-    base = [X.file_bytes("index_edge"), X.gen_vcfc(150, 77)]
-    for k in range(12):
-        v0 = base[k % 2]
-        idx0 = X.build_index(v0, 2)[1]
-        v = mutate(v0, rnd, rnd.randrange(1, 4))
-        want = X.build_index(v, 2)
-        got = emu_create(v, 2)
-        assert got == want, (seed, k, got[0], got[2], want[0], want[2])
-        for q in ("1:100-400", "2:100-2000", "X:1-100000", "foo:1-100000"):
-            st_w, out_w = X.query(v, idx0, q)
-            st, out = emu_query(v, idx0, q, window=4096)
-            if st == OK:
-                assert (st_w, out_w) == (OK, out), (seed, k, q)
-            else:   # refused: nothing but lines the restatement also writes
-                assert st == E_FORMAT and out_w.startswith(out), (seed, k, q, st)
+    EC.check_mutated_binned(EMU, seed, window=4096)
+
+
+def test_mutated_files_floor():
+    """Over the seeds the restatement takes at least 5 files whole and refuses at least 5 under each of codes 2 and 3."""
+    assert min(EC.mutated_floor(False)) >= 5, EC.mutated_floor(False)
 
 
 def test_emu_query_reads_only_its_windows():

@@ -3,10 +3,10 @@
 (tests/golden/sparse_index_cases.json), then the product kernels
 (csrc/vcfc_sparse_index.hip) and host drivers
 (csrc/vcfc_sparse_index_driver.h) compiled against the fiber SIMT emulator,
-against the goldens and the restatement.  test_gpu_sparse_index.py repeats
-the valid-input part on the GPU."""
+against the goldens and the restatement, and the hand-built edge families of
+index_edge_cases.py.  test_gpu_sparse_index.py repeats the generated inputs
+and the edge families on the GPU."""
 import ctypes
-import random
 import struct
 
 import numpy as np
@@ -15,6 +15,7 @@ import pytest
 import emu_io as E
 import golden_io as G
 import index_cases as X
+import index_edge_cases as EC
 import sparse_index_cases as SX
 
 OK, E_FORMAT = 0, 8
@@ -262,17 +263,34 @@ def test_emu_generated_records(n):
         assert emu_query(v, slots, q) == SX.query(v, slots, q)
 
 
-def test_emu_unsorted_falls_back_to_record_order():
-    v = SX.gen_vcfc(300, 17, pairs=(63, 255), unsorted=True)
-    words, _, _ = emu_device(v)
-    assert words[0] == NO_ERROR and words[3] == 1 and words[4] == NO_ERROR
+def test_restatement_matches_reference_edge_cases():
+    EC.check_pinned_sparse()
+
+
+def _create(v):
     st, slots, bad, sf, info = emu_create(v)
-    assert (st, slots, bad, sf) == SX.create(v) and info["in_order"] == 1 and info["pwrites"] == 300
-    # a slot written twice out of order: the later record stays
-    u = SX.file_bytes("unsorted")
-    st, slots, _, _, info = emu_create(u)
-    assert st == OK and info["in_order"] == 1 and struct.unpack("<BIQ", slots[SX.slot_offset(100)])[2] == \
-        sorted(struct.unpack("<BIQ", e)[2] for e in slots.values())[-2]
+    return st, slots, bad, sf, info["size"]
+
+
+class EMU:
+    """The callables index_edge_cases.py checks, on the emulator."""
+    device = staticmethod(emu_device)
+    create = staticmethod(_create)
+    query = staticmethod(emu_query)
+    span = staticmethod(emu_span)
+    gap = staticmethod(emu_gap)
+
+
+def test_emu_unsorted_falls_back_to_record_order():
+    EC.check_unsorted(EMU)
+    st, slots, bad, sf, info = emu_create(SX.gen_vcfc(300, 17, pairs=(63, 255), unsorted=True))
+    assert info["in_order"] == 1 and info["pwrites"] == 300
+    assert emu_create(SX.file_bytes("unsorted"))[4]["in_order"] == 1
+
+
+@pytest.mark.parametrize("family", sorted(EC.SPARSE))
+def test_emu_edge_family(family):
+    EC.SPARSE[family](EMU)
 
 
 def test_emu_no_records():
@@ -286,37 +304,7 @@ def test_emu_no_records():
 
 
 def test_emu_short_and_structural_records():
-    """A record shorter than the 56-byte fast-path window (S = 1, short
-    fields), structural ALTs (eight TABs and the INFO walk), fields the
-    generator does not draw, and where the two passes differ: a bad INFO stops
-    create and not the walk."""
-    rows = [b"1\t7\t.\tA\tC\t1\tPASS\t.", b"1\t 9\t.\tACG\tA\t1\tPASS\t.", b"1\t12\t.\tA\t<X>\t1\tPASS\tEND=-5, 70,+60",
-            b"1\t15\t.\tA\t<X>\t1\tPASS\tEND", b"1\t20\t.\tA\tC<\t1\tPASS\tSVLEN=18446744073709551615",
-            b"22\t30\t.\tA\t,\t1\tPASS\t.", b"M\t35\t" + b"i" * 70 + b"\tA\tCC\t1\tPASS\t.",
-            b"23\t40\t.\tA\t" + b"C" * 50 + b"<\t1\tPASS\tX=1", b"X\t36028797018963968\t.\tA\tC\t1\tPASS\t."]
-    vcf = X.header(1) + b"".join(r + b"\tGT\t0|1\n" for r in rows)
-    st, v, _ = G.oracle_compress(vcf)
-    assert st == 0
-    h, ro = rec_offsets(v)
-    assert min(ro[i + 1] - ro[i] for i in range(len(rows))) < 56
-    for walk in (0, 1):
-        err, ref, pos = emu_span(v, walk)
-        assert err == NO_ERROR and list(zip(ref, pos)) == fields_of(v, walk)
-    want = SX.create(v)
-    assert want[0] == OK and want[3] == 1 and len(want[1]) == len(rows) - 1   # POS 2^55: the offset is negative as off_t
-    assert emu_create(v)[:4] == want
-    for bad_info in (b"END=1;=", b"A=B=C", b"END=1x", b"SVLEN=3,x"):
-        st, w, _ = G.oracle_compress(X.header(1) + b"".join(r + b"\tGT\t0|1\n" for r in rows[:8]) +
-                                     b"M\t60\t.\tA\t<X>\t1\tPASS\t" + bad_info + b"\tGT\t0|1\n" +
-                                     b"M\t61\t.\tA\tC\t1\tPASS\t.\tGT\t0|1\n")
-        assert st == 0
-        got = emu_create(w)
-        assert got[:4] == SX.create(w) and got[0] == E_FORMAT and got[2] == 8 and len(got[1]) == 8, bad_info
-        assert emu_span(w, 0)[0] == (8 << 8 | 2) and emu_span(w, 1)[0] == NO_ERROR
-        slots = got[1]
-        q = "M:1-100"
-        st, out = emu_query(w, slots, q)
-        assert (st, out) == SX.query(w, slots, q) and st == OK and out.count(b"\n") == 3   # M 35, through the bad M 60, M 61
+    EC.check_short_and_structural(EMU)
 
 
 def test_emu_refused_offset_stops_the_run():
@@ -362,37 +350,14 @@ def test_emu_lookup_rules():
     assert (st, out) == SX.query(v, two, "1:101-160") and out.count(b"\n") == 1 and io == [8, 8]
 
 
-def mutate(v, rnd, patches):
-    """Random byte patches in record headers (LEN, REQ) and prefixes (CHROM .. INFO)."""
-    b = bytearray(v)
-    h, ro = rec_offsets(v)
-    for _ in range(patches):
-        r = rnd.randrange(len(ro) - 1)
-        p = h + ro[r] + rnd.choice([rnd.randrange(0, 8), rnd.randrange(8, 60)])
-        if p < len(b):
-            b[p] = rnd.choice([rnd.randrange(256), 9, 0x3C, 0x3D, 0x3B, 0x2C, 0x30])
-    return bytes(b)
-
-
-@pytest.mark.parametrize("seed", [1, 2, 3, 4])
+@pytest.mark.parametrize("seed", EC.MUTATE_SEEDS)
 def test_emu_mutated_files(seed):
-    rnd = random.Random(seed)
-    base = [SX.file_bytes("index_edge"), SX.gen_vcfc(150, 77, pairs=(63,))]
-    for k in range(12):
-        v0 = base[k % 2]
-        slots0 = SX.create(v0)[1]
-        v = mutate(v0, rnd, rnd.randrange(1, 4))
-        want = SX.create(v)
-        got = emu_create(v)
-        assert got[:4] == want, (seed, k, got[0], got[2], want[0], want[2])
-        for q in ("1:100-400", "2:100-2000", "X:1-100000", "foo:1-100000", "1:60-90"):
-            st_w, out_w = SX.query(v, slots0, q)
-            st, out = emu_query(v, slots0, q, window=4096)
-            if st == OK:
-                assert (st_w, out_w) == (OK, out), (seed, k, q)
-            else:   # refused at a malformed record: the same lines up to it (its own line may or may not decode)
-                assert st == E_FORMAT and (out_w.startswith(out) or (st_w == E_FORMAT and out.startswith(out_w))), \
-                    (seed, k, q, st)
+    EC.check_mutated_sparse(EMU, seed, window=4096)
+
+
+def test_mutated_files_floor():
+    """Over the seeds the restatement takes at least 5 files whole and refuses at least 5 under each of codes 2 and 3."""
+    assert min(EC.mutated_floor(True)) >= 5, EC.mutated_floor(True)
 
 
 def test_emu_query_reads_only_its_windows():

@@ -168,8 +168,10 @@ __global__ __launch_bounds__(256) void k_sparse_emit(const uint8_t *ref_idx, con
 // LF counts only when it ends an uncompressed column (:880-891; the LF read
 // at :958 is not counted).  The walk is dec_line_seq's (vcfc_decode.hip)
 // without its output; the exact decode plan validates the same records, so a
-// record refused here (code 3) is refused there too, except one with fewer
-// than two non-empty fields in its required columns.
+// record refused here (code 3) is refused there too, except one whose second
+// non-empty field does not lie wholly in its required columns: fewer than two
+// such fields there, or the second one ended by the columns' end with sample
+// tokens after it (the line's field then runs on into the first token).
 __global__ __launch_bounds__(256) void k_gap_fields(const uint8_t *in, const uint64_t *rec, uint64_t n, uint64_t S,
                                                     uint64_t *pos_off, uint32_t *pos_len, uint64_t *ccount,
                                                     uint64_t *err) {
@@ -190,7 +192,7 @@ __global__ __launch_bounds__(256) void k_gap_fields(const uint8_t *in, const uin
         uint32_t found = 0;
         uint64_t fs = rs + 8;
         for (uint64_t k = rs + 8; k <= s0 && found < 2; k++) {
-            if (k == s0 || in[k] == '\t') {
+            if (k == s0 ? S == 0 : in[k] == '\t') {
                 if (k > fs && ++found == 2) { po = fs; pl = (uint32_t)(k - fs); }
                 fs = k + 1;
             }
