@@ -531,9 +531,13 @@ int vcfc_decode_samples_device(const uint8_t *d_in, uint64_t in_bytes, const uin
  * decoder, up to 3 bytes past the last record's end
  * must be readable.  vcfc_counts_lds_samples(): the largest `samples` whose
  * histogram is summed in LDS (above it the general path takes global
- * atomics). */
+ * atomics).  vcfc_counts_trip_records(samples, with_sample_table): the records
+ * one pass of the scan's resident grid covers on the current device, with or
+ * without d_sample (a longer call goes round the grid again; 0 where the
+ * device cannot be asked): for tests and tuning, no argument depends on it. */
 uint64_t vcfc_counts_workspace_size(uint64_t n_records, uint64_t samples);
 uint64_t vcfc_counts_lds_samples(void);
+uint64_t vcfc_counts_trip_records(uint64_t samples, int with_sample_table);
 int vcfc_genotype_counts_device(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_rec_start,
                                 const uint8_t *d_select, uint64_t n, uint64_t samples, uint32_t *d_variant,
                                 uint64_t *d_sample, void *d_ws, uint64_t ws_bytes, uint64_t *d_err, void *stream);
@@ -671,12 +675,16 @@ int vcfc_genotype_counts_regions_file(vcfc_ctx *ctx, const char *in_vcfc, const 
  * vcfc_matrix_workspace_size(n, samples, layout).  Up to 3 bytes past the
  * last record's end must be readable.  vcfc_matrix_lds_samples(layout): the
  * largest `samples` whose row is put together in LDS (above it a byte-serial
- * path writes straight to global memory: correct, untuned). */
+ * path writes straight to global memory: correct, untuned).
+ * vcfc_matrix_trip_records(layout): the records one pass of that kernel's
+ * resident grid covers on the current device (a longer call goes round the
+ * grid again; 0 for an unknown layout or where the device cannot be asked). */
 #define VCFC_GM_DOSAGE 0
 #define VCFC_GM_HAP 1
 #define VCFC_GM_BED 2
 uint64_t vcfc_matrix_row_bytes(int layout, uint64_t samples);
 uint64_t vcfc_matrix_lds_samples(int layout);
+uint64_t vcfc_matrix_trip_records(int layout);
 uint64_t vcfc_matrix_workspace_size(uint64_t n_records, uint64_t samples, int layout);
 int vcfc_genotype_matrix_device(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_rec_start,
                                 const uint8_t *d_select, uint64_t n, uint64_t samples, int layout, uint8_t *d_out,

@@ -14,6 +14,9 @@
 #include "host_buffers.h"
 
 extern "C" uint64_t emu_counts_lds_samples() { return VCFC_COUNTS_LDS_SAMPLES; }
+extern "C" uint64_t emu_counts_trip_records(uint64_t S, int with_sample_table) {
+    return vcfc_counts_scan_trip(S, with_sample_table != 0);
+}
 extern "C" uint64_t emu_counts_workspace_size(uint64_t n, uint64_t S) { return vcfc_counts_workspace_layout(n, S).total; }
 
 // genotype-counts over a whole .vcfc (the C ABI's control flow): rows and

@@ -17,6 +17,7 @@ extern "C" uint64_t emu_extract_bound(uint64_t in_bytes, uint64_t n_records, uin
     return vcfc_ext::extract_bound(in_bytes, n_records, K);
 }
 extern "C" uint64_t emu_extract_tile(void) { return VCFC_EXTRACT_TILE; }
+extern "C" uint64_t emu_extract_workspace_size(uint64_t n, uint64_t K) { return vcfc_extract_workspace_layout(n, K).total; }
 
 static uint64_t g_sink_calls = 0;   // pieces the last emu_extract sank (header included)
 extern "C" uint64_t emu_extract_sink_calls() { return g_sink_calls; }

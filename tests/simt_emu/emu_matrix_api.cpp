@@ -16,6 +16,7 @@
 
 extern "C" uint64_t emu_matrix_row_bytes(int layout, uint64_t S) { return vcfc_matrix_row_size(layout, S); }
 extern "C" uint64_t emu_matrix_lds_samples(int layout) { return vcfc_matrix_tile_samples(layout); }
+extern "C" uint64_t emu_matrix_trip_records(int layout) { return vcfc_matrix_scan_trip(layout); }
 extern "C" uint64_t emu_matrix_workspace_size(uint64_t n, uint64_t, int) { return vcfc_matrix_workspace_layout(n).total; }
 
 // genotype-matrix over a whole .vcfc (the C ABI's control flow): indices and

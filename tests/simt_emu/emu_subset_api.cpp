@@ -16,6 +16,7 @@ using vcfc_sub::Call;
 
 static uint64_t g_sink_calls = 0;   // pieces the last emu_subset_decompress sank (header included)
 extern "C" uint64_t emu_subset_sink_calls() { return g_sink_calls; }
+extern "C" uint64_t emu_subset_workspace_size(uint64_t n, uint64_t K) { return vcfc_subset_workspace_layout(n, K).total; }
 
 // decompress-samples over a whole .vcfc (the C ABI's control flow)
 extern "C" int emu_subset_decompress(const uint8_t *in, uint64_t n, const uint32_t *cols, uint64_t K, uint8_t *out,

@@ -14,6 +14,7 @@ import counts_cases as CC
 import decode_cases as D
 import emu_io as E
 import golden_io as G
+import reader_edge_cases as RE
 import subset_cases as SC
 
 OK, E_ARG, E_FORMAT = CC.OK, CC.E_ARG, CC.E_FORMAT
@@ -267,3 +268,62 @@ def test_device_entry_irregular_record_only_where_selected():
     st, err, got, tab = emu_device(data, [int(i != 17) for i in range(n)])
     assert (st, err) == (OK, NO_ERROR) and got[:17] == rows and got[17] == [0] * 8
     assert [sum(r) for r in tab] == [n - 1] * 40
+
+
+# ---- the grid's later trips and the stager's edges (reader_edge_cases.py) ----------
+
+def emu_device_records(body, rec, S, select, variant, sample, calls):
+    """emu_counts_device on the records body[rec[i], rec[i + 1]) (rec: an
+    array of n + 1 offsets): (status, err word, rows or None, sample table or
+    None), as arrays."""
+    n = len(rec) - 1
+    r = np.ascontiguousarray(rec, dtype=np.uint64)
+    rows = np.full((n + 1, 8), 0xEEEEEEEE, dtype=np.uint32)
+    tab = np.zeros((S + 1, 5), dtype=np.uint64)
+    tab[S] = 0xEE
+    wsb = lib().emu_counts_workspace_size(n, S)
+    ws = np.full(wsb + 64, 0xCD, dtype=np.uint8)
+    err = np.zeros(1, dtype=np.uint64)
+    for _ in range(calls):
+        st = lib().emu_counts_device(body, r.ctypes.data, None if select is None else select.ctypes.data, n, S,
+                                     rows.ctypes.data if variant else None, tab.ctypes.data if sample else None,
+                                     ws.ctypes.data, wsb, err.ctypes.data)
+    assert (rows[n] == 0xEEEEEEEE).all() and (tab[S] == 0xEE).all() and (ws[wsb:] == 0xCD).all(), "written past an end"
+    return st, int(err[0]), rows[:n] if variant else None, tab[:S] if sample else None
+
+
+def trip_records(S, with_sample_table):
+    L = lib()
+    L.emu_counts_trip_records.restype = ctypes.c_uint64
+    L.emu_counts_trip_records.argtypes = [ctypes.c_uint64, ctypes.c_int]
+    return L.emu_counts_trip_records(S, int(with_sample_table))
+
+
+def test_trip_records():
+    """The emulator reports 4 CUs: two blocks a CU with the LDS tile, four
+    without, eight waves a block, 16 records a wave."""
+    L = lib().emu_counts_lds_samples()
+    assert [trip_records(5, True), trip_records(L, True), trip_records(L + 1, True), trip_records(5, False)] == \
+        [1024, 1024, 2048, 2048]
+
+
+def test_second_trip_lds():
+    assert RE.check_counts_trip(emu_device_records, trip_records, 5, True, True) == 1024 + 53
+
+
+def test_second_trip_no_table():
+    assert RE.check_counts_trip(emu_device_records, trip_records, 5, True, False) == 2048 + 53
+
+
+def test_second_trip_global():
+    L = lib().emu_counts_lds_samples()
+    RE.check_counts_trip(emu_device_records, trip_records, L + 1, False, True, L=L)
+
+
+def test_second_trip_irregular_records():
+    RE.check_counts_trip_irregular(emu_device_records, trip_records)
+
+
+@pytest.mark.parametrize("fam", RE.FAMILIES)
+def test_stager_edges(fam):
+    RE.check_edges_counts(lambda data, q: emu_run(data, q, texts=False), fam)

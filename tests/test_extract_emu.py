@@ -15,6 +15,7 @@ import decode_cases as D
 import emu_io as E
 import extract_cases as EC
 import golden_io as G
+import reader_edge_cases as RE
 import subset_cases as SC
 
 OK, E_NOSPACE, E_ARG, E_FORMAT = EC.OK, EC.E_NOSPACE, EC.E_ARG, EC.E_FORMAT
@@ -213,3 +214,25 @@ def test_device_entry():
 
 def test_bound():
     EC.check_bound(lambda a, b, c: lib().emu_extract_bound(a, b, c))
+
+
+# ---- the byte-serial lanes' later passes and the stager's edges (reader_edge_cases.py) ----
+
+def workspace_size(n, K):
+    L = lib()
+    L.emu_extract_workspace_size.restype = ctypes.c_uint64
+    L.emu_extract_workspace_size.argtypes = [ctypes.c_uint64, ctypes.c_uint64]
+    return L.emu_extract_workspace_size(n, K)
+
+
+@pytest.mark.parametrize("cols", RE.QUEUE_COLS[1:3])
+def test_queue_pass(cols):
+    """Output batches of 700 bytes and one batch."""
+    assert RE.check_queue_is_longer_than_the_lanes(workspace_size, 2) == 1024
+    exts = [lambda data, cols, ob=ob: emu_ext(data, cols, out_batch=ob) for ob in (700, 1 << 30)]
+    RE.check_queue_extract(exts, emu_device, [cols])
+
+
+@pytest.mark.parametrize("fam", RE.FAMILIES)
+def test_stager_edges(fam):
+    RE.check_edges_extract(emu_ext, fam)

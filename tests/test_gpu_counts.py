@@ -16,6 +16,7 @@ import pytest
 import counts_cases as CC
 import decode_cases as D
 import golden_io as G
+import reader_edge_cases as RE
 import subset_cases as SC
 
 pytestmark = pytest.mark.gpu
@@ -237,3 +238,82 @@ def test_file_2504_samples(ctx):
     assert rows[:, 5:].tolist() == [CC.row(t)[5:] for t in lines]
     st, idx, rows, tab = ctx.genotype_counts_buffer(enc, "1:%d-%d" % (10000 + 2 * 17, 10000 + 2 * 217))   # POS = 10000 + 2 i
     assert st == OK and idx.tolist() == list(range(17, 218)) and rows[:, :5].tolist() == want_rows[17:218]
+
+
+# ---- the grid's later trips and the stager's edges (reader_edge_cases.py) ----------
+
+def device_records(body, rec, S, select, variant, sample, calls):
+    """vcfc_genotype_counts_device on the records body[rec[i], rec[i + 1])
+    (rec: an array of n + 1 offsets): (status, err word, rows or None, sample
+    table or None), as arrays."""
+    import torch
+    import vcfc
+    n = len(rec) - 1
+    dev = "cuda:0"
+    d_in = torch.from_numpy(np.frombuffer(body + bytes(64), dtype=np.uint8).copy()).to(dev)
+    d_rec = torch.from_numpy(np.ascontiguousarray(rec, dtype=np.uint64).view(np.int64)).to(dev)
+    d_sel = None if select is None else torch.from_numpy(select).to(dev)
+    d_rows = torch.full((n + 1, 8), -0x11111112, dtype=torch.int32, device=dev)
+    init = np.zeros((S + 1, 5), dtype=np.int64)
+    init[S] = 0xEE
+    d_tab = torch.from_numpy(init).to(dev)
+    wsb = vcfc.counts_workspace_size(n, S)
+    d_ws = torch.full((wsb + 64,), 0xCD, dtype=torch.uint8, device=dev)
+    d_err = torch.zeros(1, dtype=torch.int64, device=dev)
+    for _ in range(calls):
+        st = vcfc.genotype_counts_device(d_in.data_ptr(), len(body), d_rec.data_ptr(), None if d_sel is None else d_sel.data_ptr(),
+                                         n, S, d_rows.data_ptr() if variant else None, d_tab.data_ptr() if sample else None,
+                                         d_ws.data_ptr(), wsb, d_err.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    rows = d_rows.cpu().numpy().view(np.uint32)
+    tab = d_tab.cpu().numpy().view(np.uint64)
+    assert (rows[n] == 0xEEEEEEEE).all() and (tab[S] == 0xEE).all() and (d_ws[wsb:].cpu().numpy() == 0xCD).all(), \
+        "written past an end"
+    return st, int(d_err.cpu().numpy().view(np.uint64)[0]), rows[:n] if variant else None, tab[:S] if sample else None
+
+
+def trip_records(S, with_sample_table):
+    import vcfc
+    return vcfc.counts_trip_records(S, with_sample_table)
+
+
+def test_trip_records():
+    """Whole chunks of 16 records on every CU; the LDS tile's grid up to the
+    limit, the same grid above it as without a sample table (the emulator suite
+    pins the figures)."""
+    import torch
+    import vcfc
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    L = vcfc.counts_lds_samples()
+    lds, glob, none = trip_records(5, True), trip_records(L + 1, True), trip_records(5, False)
+    assert lds > 0 and lds % (16 * cus) == 0 and trip_records(L, True) == lds
+    assert glob == none >= lds and none % (16 * cus) == 0
+
+
+def test_second_trip_lds():
+    n = RE.check_counts_trip(device_records, trip_records, 5, True, True)
+    assert n > trip_records(5, True) > 10000   # (10 000: the largest file of the other tests)
+
+
+def test_second_trip_no_table():
+    assert RE.check_counts_trip(device_records, trip_records, 5, True, False) > trip_records(5, False)
+
+
+def test_second_trip_global():
+    import vcfc
+    L = vcfc.counts_lds_samples()
+    assert RE.check_counts_trip(device_records, trip_records, L + 1, False, True, L=L) > trip_records(L + 1, True)
+
+
+def test_second_trip_irregular_records():
+    RE.check_counts_trip_irregular(device_records, trip_records)
+
+
+def test_second_trip_of_the_serial_kernel():
+    """k_cnt_seq strides over a fixed number of lanes: more queued records than that."""
+    RE.check_counts_serial_trip(device_records)
+
+
+@pytest.mark.parametrize("fam", RE.FAMILIES)
+def test_stager_edges(run, fam):
+    RE.check_edges_counts(run, fam)

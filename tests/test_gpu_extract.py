@@ -17,6 +17,7 @@ import pytest
 import decode_cases as D
 import extract_cases as EC
 import golden_io as G
+import reader_edge_cases as RE
 import regions_cases as RC
 import subset_cases as SC
 
@@ -218,3 +219,16 @@ def test_files_and_cli(ctx):
         r = subprocess.run([MAIN, "extract-samples", src, dst, "S0,S5"], capture_output=True, timeout=300)
         want = EC.extract(bad, [0, 5])
         assert r.returncode == 134 and want[0] == E_FORMAT and open(dst, "rb").read() == want[1]
+
+
+# ---- the byte-serial lanes' later passes and the stager's edges (reader_edge_cases.py) ----
+
+def test_queue_pass(ext):
+    import vcfc
+    RE.check_queue_is_longer_than_the_lanes(vcfc.extract_workspace_size, 2)
+    RE.check_queue_extract([ext], device_run)
+
+
+@pytest.mark.parametrize("fam", RE.FAMILIES)
+def test_stager_edges(ext, fam):
+    RE.check_edges_extract(ext, fam)

@@ -18,6 +18,7 @@ import pytest
 import decode_cases as D
 import golden_io as G
 import matrix_cases as MC
+import reader_edge_cases as RE
 import regions_cases as RC
 import subset_cases as SC
 
@@ -257,3 +258,38 @@ def test_file_2504_samples(ctx):
     st, idx, m = ctx.genotype_matrix_buffer(enc, MC.DOSAGE, "1:%d-%d" % (10000 + 2 * 17, 10000 + 2 * 97))   # POS = 10000 + 2 i
     assert st == OK and idx.tolist() == list(range(17, 98))
     assert [r.tobytes() for r in m] == want[MC.DOSAGE][17:98]
+
+
+# ---- the grid's later trips and the stager's edges (reader_edge_cases.py) ----------
+
+def trip_records(layout):
+    import vcfc
+    return vcfc.matrix_trip_records(layout)
+
+
+def test_trip_records():
+    """Whole chunks of 16 records on every CU; 0 for a layout there is none
+    of (the emulator suite pins the figures)."""
+    import torch
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    t = trip_records(0)
+    assert t > 0 and t % (16 * cus) == 0 and [trip_records(k) for k in (1, 2, 3)] == [t, t, 0]
+
+
+@pytest.mark.parametrize("layout", MC.LAYOUTS)
+def test_second_trip(layout):
+    assert RE.check_matrix_trip(device_run, trip_records, layout) > trip_records(layout) > 10000
+
+
+def test_second_trip_irregular_records():
+    RE.check_matrix_trip_irregular(device_run, trip_records)
+
+
+def test_second_trip_of_the_serial_kernel():
+    """k_gm_seq strides over a fixed number of lanes: more queued records than that."""
+    RE.check_matrix_serial_trip(device_run)
+
+
+@pytest.mark.parametrize("fam", RE.FAMILIES)
+def test_stager_edges(run, fam):
+    RE.check_edges_matrix(run, fam)

@@ -14,6 +14,7 @@ import pytest
 
 import decode_cases as D
 import golden_io as G
+import reader_edge_cases as RE
 import subset_cases as SC
 
 pytestmark = pytest.mark.gpu
@@ -226,3 +227,16 @@ def test_files_2504_samples(ctx):
         with open(dst, "wb") as f:
             ctx.query_samples_file(src, "1:10000-10010", cols, out_fd=f.fileno())
         assert open(dst, "rb").read() == b"".join(l + b"\n" for l in lines[0:6])
+
+
+# ---- the writer's later passes and the stager's edges (reader_edge_cases.py) --------
+
+def test_queue_pass(dec):
+    import vcfc
+    RE.check_queue_is_longer_than_the_lanes(vcfc.subset_workspace_size, 1)
+    RE.check_queue_subset([dec], device_run)
+
+
+@pytest.mark.parametrize("fam", RE.FAMILIES)
+def test_stager_edges(dec, fam):
+    RE.check_edges_subset(dec, fam)

@@ -16,6 +16,7 @@ import decode_cases as D
 import emu_io as E
 import golden_io as G
 import matrix_cases as MC
+import reader_edge_cases as RE
 import subset_cases as SC
 
 OK, E_ARG, E_FORMAT = MC.OK, MC.E_ARG, MC.E_FORMAT
@@ -216,3 +217,32 @@ def test_device_entry():
 
 def test_device_entry_arguments():
     MC.check_device_args(emu_device, lib().emu_matrix_workspace_size)
+
+
+# ---- the grid's later trips and the stager's edges (reader_edge_cases.py) ----------
+
+def trip_records(layout):
+    L = lib()
+    L.emu_matrix_trip_records.restype = ctypes.c_uint64
+    L.emu_matrix_trip_records.argtypes = [ctypes.c_int]
+    return L.emu_matrix_trip_records(layout)
+
+
+def test_trip_records():
+    """The emulator reports 4 CUs: five blocks a CU, four waves a block, 16
+    records a wave; 0 for a layout there is none of."""
+    assert [trip_records(k) for k in (0, 1, 2, 3)] == [1280, 1280, 1280, 0]
+
+
+@pytest.mark.parametrize("layout", MC.LAYOUTS)
+def test_second_trip(layout):
+    assert RE.check_matrix_trip(emu_device, trip_records, layout) == 1280 + 53
+
+
+def test_second_trip_irregular_records():
+    RE.check_matrix_trip_irregular(emu_device, trip_records)
+
+
+@pytest.mark.parametrize("fam", RE.FAMILIES)
+def test_stager_edges(fam):
+    RE.check_edges_matrix(emu_run, fam)

@@ -12,6 +12,7 @@ import pytest
 import decode_cases as D
 import emu_io as E
 import golden_io as G
+import reader_edge_cases as RE
 import subset_cases as SC
 
 OK, E_ARG, E_FORMAT = SC.OK, SC.E_ARG, SC.E_FORMAT
@@ -35,9 +36,9 @@ def lib():
     return L
 
 
-def emu_dec(data, cols, out_batch=1 << 14):
+def emu_dec(data, cols, out_batch=1 << 14, cap=None):
     c = np.array(cols, dtype=np.uint32)
-    cap = len(data) * 8 + 4096
+    cap = len(data) * 8 + 4096 if cap is None else cap
     out = np.zeros(cap, dtype=np.uint8)
     n = ctypes.c_uint64(0)
     st = lib().emu_subset_decompress(data, len(data), c.ctypes.data, len(cols), out.ctypes.data, cap, ctypes.byref(n),
@@ -233,3 +234,26 @@ def test_sample_columns():
     n, bad = ctypes.c_uint64(0), ctypes.c_uint64(0)
     assert lib().emu_sample_columns(rep, len(rep), b"S6", 2, cols.ctypes.data, 4, ctypes.byref(n), ctypes.byref(bad)) == OK
     assert int(cols[0]) == 6
+
+
+# ---- the writer's later passes and the stager's edges (reader_edge_cases.py) --------
+
+def workspace_size(n, K):
+    L = lib()
+    L.emu_subset_workspace_size.restype = ctypes.c_uint64
+    L.emu_subset_workspace_size.argtypes = [ctypes.c_uint64, ctypes.c_uint64]
+    return L.emu_subset_workspace_size(n, K)
+
+
+@pytest.mark.parametrize("cols", RE.QUEUE_COLS[1:3])
+def test_queue_pass(cols):
+    """Output batches of 700 bytes (a handful of lines each, so a lane's
+    second record falls in another batch than its first) and one batch."""
+    assert RE.check_queue_is_longer_than_the_lanes(workspace_size, 1) == 1024
+    decs = [lambda data, cols, ob=ob: emu_dec(data, cols, out_batch=ob) for ob in (700, 1 << 30)]
+    RE.check_queue_subset(decs, emu_device, [cols])
+
+
+@pytest.mark.parametrize("fam", RE.FAMILIES)
+def test_stager_edges(fam):
+    RE.check_edges_subset(lambda data, cols: emu_dec(data, cols, cap=D.edge_cap(data)), fam)

@@ -1361,6 +1361,10 @@ uint64_t vcfc_counts_workspace_size(uint64_t n_records, uint64_t samples) {
 
 uint64_t vcfc_counts_lds_samples(void) { return VCFC_COUNTS_LDS_SAMPLES; }
 
+uint64_t vcfc_counts_trip_records(uint64_t samples, int with_sample_table) {
+    return vcfc_counts_scan_trip(samples, with_sample_table != 0);
+}
+
 int vcfc_genotype_counts_device(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_rec_start,
                                 const uint8_t *d_select, uint64_t n, uint64_t samples, uint32_t *d_variant,
                                 uint64_t *d_sample, void *d_ws, uint64_t ws_bytes, uint64_t *d_err, void *stream) {
@@ -1656,6 +1660,8 @@ int vcfc_genotype_counts_regions_file(vcfc_ctx *c, const char *in_path, const ch
 uint64_t vcfc_matrix_row_bytes(int layout, uint64_t samples) { return vcfc_matrix_row_size(layout, samples); }
 
 uint64_t vcfc_matrix_lds_samples(int layout) { return vcfc_matrix_tile_samples(layout); }
+
+uint64_t vcfc_matrix_trip_records(int layout) { return vcfc_matrix_scan_trip(layout); }
 
 uint64_t vcfc_matrix_workspace_size(uint64_t n_records, uint64_t, int) {
     return vcfc_matrix_workspace_layout(n_records).total;

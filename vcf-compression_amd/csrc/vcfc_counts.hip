@@ -329,7 +329,31 @@ void launch_scan(const VcfcCountsArgs &a, unsigned blocks, hipStream_t s) {
     hipLaunchKernelGGL((k_cnt_scan<SEL, HIST>), dim3(blocks), dim3(64 * CNT_WAVES), 0, s, a);
 }
 
+// the histogram k_cnt_scan is launched with
+int hist_of(uint64_t S, bool with_sample_table) {
+    return !with_sample_table ? H_NONE : S <= VCFC_COUNTS_LDS_SAMPLES ? H_LDS : H_GLOBAL;
+}
+
+// as many blocks of k_cnt_scan as stay resident on the current device (two
+// per CU with the tile, four without), so each tile is flushed once over many
+// records
+hipError_t resident_blocks(int hist, uint64_t *blocks) {
+    int dev = 0, cus = 0;
+    hipError_t e;
+    if ((e = hipGetDevice(&dev)) != hipSuccess ||
+        (e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess)
+        return e;
+    *blocks = (hist == H_LDS ? 2ull : 4ull) * (uint64_t)(cus > 0 ? cus : 1);
+    return hipSuccess;
+}
+
 }  // namespace
+
+uint64_t vcfc_counts_scan_trip(uint64_t S, bool with_sample_table) {
+    uint64_t blocks = 0;
+    if (resident_blocks(hist_of(S, with_sample_table), &blocks) != hipSuccess) return 0;
+    return blocks * CNT_WAVES * CNT_CH;
+}
 
 VcfcCountsLayout vcfc_counts_workspace_layout(uint64_t n, uint64_t S) {
     auto al = [](uint64_t x) { return (x + 255) & ~255ull; };
@@ -349,15 +373,10 @@ hipError_t vcfc_counts_run(const VcfcCountsArgs &a, hipStream_t s) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || a.n == 0) return e;
     if (a.sample && (e = hipMemsetAsync(a.hist, 0, 32 * a.S, s)) != hipSuccess) return e;
-    // as many blocks as stay resident (two per CU with the tile, four
-    // without), so each tile is flushed once over many records
-    int dev = 0, cus = 0;
-    if ((e = hipGetDevice(&dev)) != hipSuccess ||
-        (e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess)
-        return e;
     const uint64_t chunk = (uint64_t)CNT_WAVES * CNT_CH;
-    const int hist = !a.sample ? H_NONE : a.S <= VCFC_COUNTS_LDS_SAMPLES ? H_LDS : H_GLOBAL;
-    const uint64_t max_blocks = (hist == H_LDS ? 2ull : 4ull) * (uint64_t)(cus > 0 ? cus : 1);
+    const int hist = hist_of(a.S, a.sample != nullptr);
+    uint64_t max_blocks = 0;
+    if ((e = resident_blocks(hist, &max_blocks)) != hipSuccess) return e;
     const uint64_t blocks = std::min<uint64_t>(max_blocks, (a.n + chunk - 1) / chunk);
     const unsigned g = (unsigned)blocks;
     if (a.select) {

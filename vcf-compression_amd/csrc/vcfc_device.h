@@ -334,6 +334,9 @@ inline void vcfc_counts_args_workspace(VcfcCountsArgs &a, uint8_t *ws, const Vcf
 // one scan of every (selected) record: rows, the sample table, err (no host
 // synchronisation)
 hipError_t vcfc_counts_run(const VcfcCountsArgs &a, hipStream_t s);
+// records one pass of the scan's resident grid covers on the current device
+// (a longer call goes round the grid again); 0 where the device cannot be asked
+uint64_t vcfc_counts_scan_trip(uint64_t S, bool with_sample_table);
 
 // ---------------------------------------------------------------------------
 // Genotype matrix (vcfc_matrix.hip): per (selected) record one
@@ -386,6 +389,10 @@ inline void vcfc_matrix_args_workspace(VcfcMatrixArgs &a, uint8_t *ws, const Vcf
 // row_of, then one pass over every (selected) record: its row, err (no host
 // synchronisation)
 hipError_t vcfc_matrix_run(const VcfcMatrixArgs &a, hipStream_t s);
+// records one pass of the scan's resident grid covers on the current device
+// (S <= vcfc_matrix_tile_samples(layout)); 0 for an unknown layout or where
+// the device cannot be asked
+uint64_t vcfc_matrix_scan_trip(int layout);
 
 // ---------------------------------------------------------------------------
 // Range query (vcfc_decode.hip; reference query_compressed_file,

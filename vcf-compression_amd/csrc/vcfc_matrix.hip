@@ -301,27 +301,45 @@ __global__ __launch_bounds__(256) void k_gm_flags(const uint8_t *select, uint32_
     if (i < n) flag32[i] = select[i] != 0;
 }
 
+// as many blocks of k_gm_scan as stay resident on the current device, so a
+// wave's tile and staging buffer serve many records
+hipError_t resident_blocks(uint64_t *blocks) {
+    int dev = 0, cus = 0;
+    hipError_t e;
+    if ((e = hipGetDevice(&dev)) != hipSuccess ||
+        (e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess)
+        return e;
+    *blocks = (uint64_t)GM_BLOCKS_PER_CU * (uint64_t)(cus > 0 ? cus : 1);
+    return hipSuccess;
+}
+
 template <int LAYOUT>
-hipError_t launch_rows(const VcfcMatrixArgs &a, int cus, hipStream_t s) {
+hipError_t launch_rows(const VcfcMatrixArgs &a, hipStream_t s) {
     const uint64_t want = (a.n + 255) / 256;
     const dim3 sg((unsigned)(want < 1024 ? want : 1024));
     if (a.S > vcfc_matrix_tile_samples(LAYOUT)) {
         hipLaunchKernelGGL((k_gm_seq<LAYOUT, true>), sg, dim3(256), 0, s, a);
         return hipGetLastError();
     }
-    // as many blocks as stay resident, so a wave's tile and staging buffer serve many records
     const uint64_t chunk = (uint64_t)GM_WAVES * GM_CH;
-    const uint64_t max_blocks = (uint64_t)GM_BLOCKS_PER_CU * (uint64_t)(cus > 0 ? cus : 1);
+    uint64_t max_blocks = 0;
+    hipError_t e = resident_blocks(&max_blocks);
+    if (e != hipSuccess) return e;
     const unsigned g = (unsigned)std::min<uint64_t>(max_blocks, (a.n + chunk - 1) / chunk);
     if (a.select) hipLaunchKernelGGL((k_gm_scan<true, LAYOUT>), dim3(g), dim3(64 * GM_WAVES), 0, s, a);
     else hipLaunchKernelGGL((k_gm_scan<false, LAYOUT>), dim3(g), dim3(64 * GM_WAVES), 0, s, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
+    if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL((k_gm_seq<LAYOUT, false>), sg, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
 }  // namespace
+
+uint64_t vcfc_matrix_scan_trip(int layout) {
+    uint64_t blocks = 0;
+    if (vcfc_matrix_tile_samples(layout) == 0 || resident_blocks(&blocks) != hipSuccess) return 0;
+    return blocks * GM_WAVES * GM_CH;
+}
 
 VcfcMatrixLayout vcfc_matrix_workspace_layout(uint64_t n) {
     auto al = [](uint64_t x) { return (x + 255) & ~255ull; };
@@ -347,13 +365,9 @@ hipError_t vcfc_matrix_run(const VcfcMatrixArgs &a, hipStream_t s) {
         hipLaunchKernelGGL(k_gm_iota, dim3((unsigned)(a.n / 256 + 1)), dim3(256), 0, s, a.row_of, a.n);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    int dev = 0, cus = 0;
-    if ((e = hipGetDevice(&dev)) != hipSuccess ||
-        (e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess)
-        return e;
     switch (a.layout) {
-    case VCFC_MATRIX_DOSAGE: return launch_rows<VCFC_MATRIX_DOSAGE>(a, cus, s);
-    case VCFC_MATRIX_HAP: return launch_rows<VCFC_MATRIX_HAP>(a, cus, s);
-    default: return launch_rows<VCFC_MATRIX_BED>(a, cus, s);
+    case VCFC_MATRIX_DOSAGE: return launch_rows<VCFC_MATRIX_DOSAGE>(a, s);
+    case VCFC_MATRIX_HAP: return launch_rows<VCFC_MATRIX_HAP>(a, s);
+    default: return launch_rows<VCFC_MATRIX_BED>(a, s);
     }
 }

@@ -53,13 +53,14 @@ EXPORTS = [
     "vcfc_sample_columns", "vcfc_subset_workspace_size", "vcfc_decode_samples_device",
     "vcfc_decompress_samples_buffer", "vcfc_decompress_samples_file",
     "vcfc_query_samples_buffer", "vcfc_query_samples_file",
-    "vcfc_counts_workspace_size", "vcfc_counts_lds_samples", "vcfc_genotype_counts_device",
+    "vcfc_counts_workspace_size", "vcfc_counts_lds_samples", "vcfc_counts_trip_records", "vcfc_genotype_counts_device",
     "vcfc_genotype_counts_buffer", "vcfc_genotype_counts_file",
     "vcfc_regions_build", "vcfc_regions_workspace_size", "vcfc_regions_upload", "vcfc_regions_match_device",
     "vcfc_query_regions_buffer", "vcfc_query_regions_file",
     "vcfc_query_samples_regions_buffer", "vcfc_query_samples_regions_file",
     "vcfc_genotype_counts_regions_buffer", "vcfc_genotype_counts_regions_file",
-    "vcfc_matrix_row_bytes", "vcfc_matrix_lds_samples", "vcfc_matrix_workspace_size", "vcfc_genotype_matrix_device",
+    "vcfc_matrix_row_bytes", "vcfc_matrix_lds_samples", "vcfc_matrix_trip_records", "vcfc_matrix_workspace_size",
+    "vcfc_genotype_matrix_device",
     "vcfc_genotype_matrix_buffer", "vcfc_genotype_matrix_regions_buffer", "vcfc_export_bed_file",
     "vcfc_export_bed_regions_file",
     "vcfc_extract_bound", "vcfc_extract_workspace_size", "vcfc_extract_samples_device", "vcfc_extract_buffer",
@@ -138,6 +139,7 @@ def lib():
             # genotype counts
             "vcfc_counts_workspace_size": [u64, u64],
             "vcfc_counts_lds_samples": [],
+            "vcfc_counts_trip_records": [u64, ctypes.c_int],
             "vcfc_genotype_counts_device": [vp, u64, vp, vp, u64, u64, vp, vp, vp, u64, vp, vp],
             "vcfc_genotype_counts_buffer": [vp, vp, u64, ctypes.c_int, ctypes.c_char_p, u64, ctypes.c_int, u64, u64, vp,
                                             vp, u64, ctypes.POINTER(u64), vp, u64, ctypes.POINTER(u64),
@@ -160,6 +162,7 @@ def lib():
             # the genotype matrix
             "vcfc_matrix_row_bytes": [ctypes.c_int, u64],
             "vcfc_matrix_lds_samples": [ctypes.c_int],
+            "vcfc_matrix_trip_records": [ctypes.c_int],
             "vcfc_matrix_workspace_size": [u64, u64, ctypes.c_int],
             "vcfc_genotype_matrix_device": [vp, u64, vp, vp, u64, u64, ctypes.c_int, vp, u64, u64, vp, vp, u64, vp, vp],
             "vcfc_genotype_matrix_buffer": [vp, vp, u64, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, u64, ctypes.c_int,
@@ -187,7 +190,7 @@ def lib():
                  "vcfc_decode_sizes_workspace_size", "vcfc_subset_workspace_size", "vcfc_counts_workspace_size",
                  "vcfc_counts_lds_samples", "vcfc_regions_workspace_size", "vcfc_matrix_row_bytes",
                  "vcfc_matrix_lds_samples", "vcfc_matrix_workspace_size", "vcfc_extract_bound",
-                 "vcfc_extract_workspace_size"):
+                 "vcfc_extract_workspace_size", "vcfc_counts_trip_records", "vcfc_matrix_trip_records"):
         if hasattr(L, name):
             getattr(L, name).restype = u64
     L.vcfc_record_hash_device.argtypes = [vp, vp, u64, vp, vp]
@@ -1235,6 +1238,12 @@ def counts_lds_samples():
     return int(_need("vcfc_counts_lds_samples")())
 
 
+def counts_trip_records(samples, with_sample_table=True):
+    """The records one pass of the counts kernel's resident grid covers on the
+    current device, with or without the sample table."""
+    return int(_need("vcfc_counts_trip_records")(samples, int(bool(with_sample_table))))
+
+
 def genotype_counts_device(d_in, in_bytes, d_rec_start, d_select, n, samples, d_variant, d_sample, d_ws, ws_bytes, d_err,
                            stream=0):
     """Rows (d_variant: 8 n uint32) and the per-sample table (d_sample: 5 S
@@ -1256,6 +1265,11 @@ def matrix_row_bytes(layout, samples):
 def matrix_lds_samples(layout):
     """The largest sample count whose row the matrix kernel puts together in LDS."""
     return int(_need("vcfc_matrix_lds_samples")(layout))
+
+
+def matrix_trip_records(layout):
+    """The records one pass of the matrix kernel's resident grid covers on the current device."""
+    return int(_need("vcfc_matrix_trip_records")(layout))
 
 
 def matrix_workspace_size(n_records, samples, layout):
