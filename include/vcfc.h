@@ -719,6 +719,76 @@ int vcfc_export_bed_file(vcfc_ctx *ctx, const char *in_vcfc, const char *out_pre
 int vcfc_export_bed_regions_file(vcfc_ctx *ctx, const char *in_vcfc, const char *out_prefix, const uint8_t *table,
                                  uint64_t table_bytes);
 
+/* ---- LD window: ld-window, ld-window-regions (no reference
+ * action: the oracle is a plain restatement over the .bed rows) ----------------
+ * Pairwise genotype tables of nearby rows of the genotype matrix.  The rows
+ * are vcfc_genotype_matrix_*'s (every record, or the records a region or a
+ * region table matches; dense, in file order; the same regular-record and
+ * stop rules), and the window is in row space.  The genotype of a sample in a
+ * row is its VCFC_GM_BED code: 11 -> 0, 10 -> 1, 00 -> 2, 01 -> missing;
+ * columns >= samples do not exist.  For rows i < j, t[3 a + b] = the samples
+ * with g_i = a and g_j = b, both called: nine uint32.  With window = W >= 1,
+ * slot i * W + (k - 1) holds the table of rows (i, i + k), k = 1..W, and nine
+ * zeros where row i + k does not exist; nothing outside slots [0, rows * W)
+ * is written.  r2 of a table, with N = sum t, Sx = sum a t, Sy = sum b t,
+ * Sxx = sum a^2 t, Syy = sum b^2 t, Sxy = sum a b t (exact in int64): cov =
+ * N Sxy - Sx Sy, vx = N Sxx - Sx^2, vy = N Syy - Sy^2; undefined where vx == 0
+ * or vy == 0, else ((double)cov * (double)cov) / ((double)vx * (double)vy).
+ * The device delivers the integers only.
+ *
+ * vcfc_ld_tables_device: the pair step on .bed rows the caller holds (row r at
+ * d_bed + r * row_stride, any row_stride >= row_bytes, any alignment; the
+ * aligned 4-byte words that hold a row's bytes are read).  d_tables: 4-byte
+ * aligned.  *d_err = ~0, or (r << 8 | 0xFF) where n_rows * window >
+ * pairs_cap: r = pairs_cap / window is the first row that is not written
+ * (a row's slots are written all or none), and nothing is written at or past
+ * slot pairs_cap.  vcfc_ld_window_device: the composed call on device-resident
+ * records, arguments as vcfc_genotype_matrix_device's: that call (layout
+ * VCFC_GM_BED) writes the rows into the workspace, then bit planes, then
+ * pairs, all enqueued on `stream` with no host synchronisation and per-call
+ * state reset by a kernel (capturable).  d_row_of as there (n + 1 words).
+ * *d_err is the matrix call's word: (i << 8 | 3) for a selected record that is
+ * not regular -- tables that touch rows >= d_row_of[i] are then not
+ * meaningful --, min'ed with (i << 8 | 0xFF) for the first record i whose
+ * row's slots do not all fit pairs_cap.  VCFC_E_ARG: window == 0 or >= 2^16,
+ * samples == 0 or >= 2^30, n (n_rows) >= 2^32, row_stride < row_bytes, a null
+ * d_tables, d_row_of, d_ws or d_err, ws_bytes below
+ * vcfc_ld_workspace_size(n, samples, window). */
+uint64_t vcfc_ld_workspace_size(uint64_t n_records, uint64_t samples, uint64_t window);
+int vcfc_ld_tables_device(const uint8_t *d_bed, uint64_t n_rows, uint64_t row_stride, uint64_t samples, uint64_t window,
+                          uint32_t *d_tables, uint64_t pairs_cap, void *d_ws, uint64_t ws_bytes, uint64_t *d_err,
+                          void *stream);
+int vcfc_ld_window_device(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_rec_start, const uint8_t *d_select,
+                          uint64_t n, uint64_t samples, uint64_t window, uint32_t *d_tables, uint64_t pairs_cap,
+                          uint64_t *d_row_of, void *d_ws, uint64_t ws_bytes, uint64_t *d_err, void *stream);
+/* A whole .vcfc in host memory.  rec_index[0, *n_rows) = the rows' records'
+ * file indices (room for rows_cap), tables = the band, *n_rows * window slots
+ * of nine words (room for pairs_cap slots).  VCFC_E_NOSPACE if either is
+ * short: *n_rows then gives the rows.  On VCFC_E_FORMAT the result is exactly
+ * the band of the rows before the failing record, as if the file ended there,
+ * and *err_record is its file index (the record count where hopping stopped
+ * short).  The _regions entry takes a built table (vcfc_regions_build). */
+int vcfc_ld_window_buffer(vcfc_ctx *ctx, const uint8_t *in, uint64_t in_bytes, uint64_t window, int has_query,
+                          const char *ref, uint64_t ref_len, int has_range, uint64_t start, uint64_t end,
+                          uint64_t *rec_index, uint64_t rows_cap, uint32_t *tables, uint64_t pairs_cap, uint64_t *n_rows,
+                          uint64_t *err_record);
+int vcfc_ld_window_regions_buffer(vcfc_ctx *ctx, const uint8_t *in, uint64_t in_bytes, uint64_t window,
+                                  const uint8_t *table, uint64_t table_bytes, uint64_t *rec_index, uint64_t rows_cap,
+                                  uint32_t *tables, uint64_t pairs_cap, uint64_t *n_rows, uint64_t *err_record);
+/* out_tsv is opened (created, truncated) before the input is parsed.  The line
+ * "#CHROM_A\tPOS_A\tID_A\tCHROM_B\tPOS_B\tID_B\tN\tR2\n", then one line per
+ * written pair in slot order: REQ's TAB fields 0, 1, 2 of both records
+ * verbatim, N in decimal, r2 as printf's %.6g or "nan" where it is undefined.
+ * A pair whose CHROM fields differ bytewise is skipped.  min_r2 > 0: a pair is
+ * written iff r2 is defined and r2 >= min_r2; min_r2 <= 0: every same-CHROM
+ * pair is written.  On VCFC_E_FORMAT past the header the pairs among the rows
+ * before the failing record are written; a header that is refused leaves the
+ * file empty. */
+int vcfc_ld_window_file(vcfc_ctx *ctx, const char *in_vcfc, const char *out_tsv, uint64_t window, double min_r2,
+                        int has_query, const char *ref, uint64_t ref_len, int has_range, uint64_t start, uint64_t end);
+int vcfc_ld_window_regions_file(vcfc_ctx *ctx, const char *in_vcfc, const char *out_tsv, uint64_t window, double min_r2,
+                                const uint8_t *table, uint64_t table_bytes);
+
 /* ---- extract: extract-samples, extract-regions (no reference
  * action: the oracle is the reference's own compress of the cut text) ----------
  * A sample / region subset of a .vcfc, written as a .vcfc; no record becomes

@@ -395,6 +395,37 @@ hipError_t vcfc_matrix_run(const VcfcMatrixArgs &a, hipStream_t s);
 uint64_t vcfc_matrix_scan_trip(int layout);
 
 // ---------------------------------------------------------------------------
+// LD window (vcfc_ld.hip): the 3 x 3 genotype table of every
+// pair of .bed rows (i, i + k), k = 1..W, by AND + population count over three
+// bit planes a row (H: g = 1, B: g = 2, V: called; 32 samples a word).
+#define VCFC_LD_TILE_ROWS 16u        // rows i one block of k_ld_pairs owns
+#define VCFC_LD_TILE_PARTNERS 64u    // partners k one block covers (gridDim.y tiles of them)
+#define VCFC_LD_CHUNK_SAMPLES 512u   // samples of every staged row in LDS at a time
+struct VcfcLdArgs {
+    const uint8_t *bed;         // .bed rows, row r at bed + r * row_stride (any alignment)
+    uint64_t row_stride;
+    uint64_t n;                 // rows at most (the grids are sized by it)
+    const uint64_t *rows_dev;   // device word that holds the row count (<= n), or nullptr: n rows
+    const uint8_t *select;      // with rows_dev: the records' flags (or nullptr) and row_of, for the
+    const uint64_t *row_of;     //   record a short pairs_cap is reported at
+    uint64_t S, W;
+    uint32_t *tables;           // slot i * W + k - 1: nine words; nothing at or past slot pairs_cap
+    uint64_t pairs_cap;
+    uint64_t *err;
+    bool own_err;               // the call resets err itself (no matrix call before it)
+    // workspace (vcfc_ld_workspace_layout)
+    uint64_t *state;            // [0] rows, [1] rows whose W slots all lie inside pairs_cap
+    uint32_t *planes;           // row r, plane p at planes + (3 r + p) * plane_words
+    uint64_t plane_words;       // a multiple of 4 (16 bytes)
+};
+struct VcfcLdLayout {
+    uint64_t state, planes, bed, bed_stride, plane_words, matrix, total;
+};
+VcfcLdLayout vcfc_ld_workspace_layout(uint64_t n, uint64_t S);
+// reset, planes, pairs: enqueued on s, no host synchronisation
+hipError_t vcfc_ld_run(const VcfcLdArgs &a, hipStream_t s);
+
+// ---------------------------------------------------------------------------
 // Range query (vcfc_decode.hip; reference query_compressed_file,
 // src/main.cpp:3777-3929).  `ref` is device memory.
 struct VcfcQuery {

@@ -63,6 +63,8 @@ EXPORTS = [
     "vcfc_genotype_matrix_device",
     "vcfc_genotype_matrix_buffer", "vcfc_genotype_matrix_regions_buffer", "vcfc_export_bed_file",
     "vcfc_export_bed_regions_file",
+    "vcfc_ld_workspace_size", "vcfc_ld_tables_device", "vcfc_ld_window_device", "vcfc_ld_window_buffer",
+    "vcfc_ld_window_regions_buffer", "vcfc_ld_window_file", "vcfc_ld_window_regions_file",
     "vcfc_extract_bound", "vcfc_extract_workspace_size", "vcfc_extract_samples_device", "vcfc_extract_buffer",
     "vcfc_extract_file", "vcfc_extract_regions_buffer", "vcfc_extract_regions_file",
 ]
@@ -173,6 +175,17 @@ def lib():
             "vcfc_export_bed_file": [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, u64,
                                      ctypes.c_int, u64, u64],
             "vcfc_export_bed_regions_file": [vp, ctypes.c_char_p, ctypes.c_char_p, vp, u64],
+            # the LD window
+            "vcfc_ld_workspace_size": [u64, u64, u64],
+            "vcfc_ld_tables_device": [vp, u64, u64, u64, u64, vp, u64, vp, u64, vp, vp],
+            "vcfc_ld_window_device": [vp, u64, vp, vp, u64, u64, u64, vp, u64, vp, vp, u64, vp, vp],
+            "vcfc_ld_window_buffer": [vp, vp, u64, u64, ctypes.c_int, ctypes.c_char_p, u64, ctypes.c_int, u64, u64, vp, u64,
+                                      vp, u64, ctypes.POINTER(u64), ctypes.POINTER(u64)],
+            "vcfc_ld_window_regions_buffer": [vp, vp, u64, u64, vp, u64, vp, u64, vp, u64, ctypes.POINTER(u64),
+                                              ctypes.POINTER(u64)],
+            "vcfc_ld_window_file": [vp, ctypes.c_char_p, ctypes.c_char_p, u64, ctypes.c_double, ctypes.c_int,
+                                    ctypes.c_char_p, u64, ctypes.c_int, u64, u64],
+            "vcfc_ld_window_regions_file": [vp, ctypes.c_char_p, ctypes.c_char_p, u64, ctypes.c_double, vp, u64],
             # extract
             "vcfc_extract_bound": [u64, u64, u64],
             "vcfc_extract_workspace_size": [u64, u64],
@@ -190,7 +203,8 @@ def lib():
                  "vcfc_decode_sizes_workspace_size", "vcfc_subset_workspace_size", "vcfc_counts_workspace_size",
                  "vcfc_counts_lds_samples", "vcfc_regions_workspace_size", "vcfc_matrix_row_bytes",
                  "vcfc_matrix_lds_samples", "vcfc_matrix_workspace_size", "vcfc_extract_bound",
-                 "vcfc_extract_workspace_size", "vcfc_counts_trip_records", "vcfc_matrix_trip_records"):
+                 "vcfc_extract_workspace_size", "vcfc_counts_trip_records", "vcfc_matrix_trip_records",
+                 "vcfc_ld_workspace_size"):
         if hasattr(L, name):
             getattr(L, name).restype = u64
     L.vcfc_record_hash_device.argtypes = [vp, vp, u64, vp, vp]
@@ -755,6 +769,62 @@ class Context:
             int(query.has_range) if query is not None else 0, query.start if query is not None else 0,
             query.end if query is not None else 0))
 
+    def ld_window_buffer(self, data, window, query=None, regions=None):
+        """ld-window over .vcfc bytes: the 3 x 3 genotype tables
+        of the pairs of rows (i, i + k), k = 1..window, the rows being
+        genotype_matrix_buffer's (every record, or those matching `query` or
+        `regions`).  Returns (status, record_indices, tables uint32[rows,
+        window, 3, 3]): tables[i, k - 1, a, b] = the samples with genotype a in
+        row i and b in row i + k, both called; zeros where row i + k does not
+        exist.  On VCFC_E_FORMAT the band is that of the rows before the
+        failing record (`last_ld_record`: its file index); any other failure
+        returns no rows.  ld_r2(tables) gives r2."""
+        if query is not None and regions is not None:
+            raise ValueError("query and regions exclude each other")
+        if query is not None and not isinstance(query, VcfCoordinateQuery):
+            query = parse_coordinate_string(query)
+        src = np.frombuffer(data, dtype=np.uint8)
+        tab = np.frombuffer(_regions_table(regions), dtype=np.uint8) if regions is not None else None
+        ref = query.reference_name if query is not None else b""
+        W = max(1, int(window)) if int(window) < 1 << 16 else 1
+        cap = len(data) // 12 + 16
+        while True:
+            idx, tables = np.zeros(cap, dtype=np.uint64), np.zeros(cap * W * 9, dtype=np.uint32)
+            n, bad = ctypes.c_uint64(0), ctypes.c_uint64(0)
+            if tab is not None:
+                st = _need("vcfc_ld_window_regions_buffer")(
+                    self._h, src.ctypes.data, len(data), window, tab.ctypes.data, len(tab), idx.ctypes.data, cap,
+                    tables.ctypes.data, cap * W, ctypes.byref(n), ctypes.byref(bad))
+            else:
+                st = _need("vcfc_ld_window_buffer")(
+                    self._h, src.ctypes.data, len(data), window, int(query is not None), ref, len(ref),
+                    int(query.has_range) if query is not None else 0, query.start if query is not None else 0,
+                    query.end if query is not None else 0, idx.ctypes.data, cap, tables.ctypes.data, cap * W,
+                    ctypes.byref(n), ctypes.byref(bad))
+            if st == E_NOSPACE and n.value > cap:
+                cap = n.value
+                continue
+            self.last_ld_record = bad.value
+            return st, idx[:n.value].copy(), tables[:n.value * W * 9].reshape(n.value, W, 3, 3).copy()
+
+    def ld_window_file(self, in_path, out_tsv, window, min_r2=0.0, query=None, regions=None):
+        """As `main ld-window <in.vcfc> <out.tsv> <window> <min-r2> [<query>]`
+        or, with `regions`, `main ld-window-regions`: one text line per pair."""
+        if query is not None and regions is not None:
+            raise ValueError("query and regions exclude each other")
+        if regions is not None:
+            tab = np.frombuffer(_regions_table(regions), dtype=np.uint8)
+            raise_for(_need("vcfc_ld_window_regions_file")(self._h, in_path.encode(), out_tsv.encode(), window, min_r2,
+                                                           tab.ctypes.data, len(tab)))
+            return
+        if query is not None and not isinstance(query, VcfCoordinateQuery):
+            query = parse_coordinate_string(query)
+        ref = query.reference_name if query is not None else b""
+        raise_for(_need("vcfc_ld_window_file")(
+            self._h, in_path.encode(), out_tsv.encode(), window, min_r2, int(query is not None), ref, len(ref),
+            int(query.has_range) if query is not None else 0, query.start if query is not None else 0,
+            query.end if query is not None else 0))
+
     def extract_buffer(self, data, cols=None, query=None, regions=None, cap=None):
         """extract: the 0-based sample columns `cols` (None:
         all) of the records `query` or `regions` match (neither: all), as a
@@ -1284,3 +1354,44 @@ def genotype_matrix_device(d_in, in_bytes, d_rec_start, d_select, n, samples, la
     Returns the status; enqueued on `stream`."""
     return _need("vcfc_genotype_matrix_device")(d_in, in_bytes, d_rec_start, d_select, n, samples, layout, d_out, out_cap,
                                                 row_stride, d_row_of, d_ws, ws_bytes, d_err, stream)
+
+
+def ld_workspace_size(n_records, samples, window):
+    return int(_need("vcfc_ld_workspace_size")(n_records, samples, window))
+
+
+def ld_tables_device(d_bed, n_rows, row_stride, samples, window, d_tables, pairs_cap, d_ws, ws_bytes, d_err, stream=0):
+    """The genotype tables of device-resident .bed rows (include/vcfc.h
+    vcfc_ld_tables_device): slot i * window + k - 1 of d_tables (nine uint32)
+    is the table of rows (i, i + k).  Asynchronous on `stream`."""
+    return _need("vcfc_ld_tables_device")(d_bed, n_rows, row_stride, samples, window, d_tables, pairs_cap, d_ws, ws_bytes,
+                                          d_err, stream)
+
+
+def ld_window_device(d_in, in_bytes, d_rec_start, d_select, n, samples, window, d_tables, pairs_cap, d_row_of, d_ws,
+                     ws_bytes, d_err, stream=0):
+    """The composed call on device-resident records (include/vcfc.h
+    vcfc_ld_window_device): .bed rows into the workspace, bit planes, pairs;
+    d_row_of[n] = the rows.  Asynchronous on `stream`, capturable."""
+    return _need("vcfc_ld_window_device")(d_in, in_bytes, d_rec_start, d_select, n, samples, window, d_tables, pairs_cap,
+                                          d_row_of, d_ws, ws_bytes, d_err, stream)
+
+
+def ld_r2(tables):
+    """r2 of genotype tables (any shape ending in 3, 3, or in 9): float64, nan
+    where it is undefined (no variance in either row among the samples called
+    in both).  Integers exact in int64, then ((double)cov * (double)cov) /
+    ((double)vx * (double)vy), as the C library's text output."""
+    t = np.asarray(tables).astype(np.int64)
+    t = t.reshape(t.shape[:-1] + (3, 3)) if t.shape[-1] == 9 else t
+    a = np.arange(3, dtype=np.int64)
+    row, col = t.sum(axis=-1), t.sum(axis=-2)
+    N = row.sum(axis=-1)
+    sx, sy = (row * a).sum(axis=-1), (col * a).sum(axis=-1)
+    sxx, syy = (row * a * a).sum(axis=-1), (col * a * a).sum(axis=-1)
+    sxy = (t * np.outer(a, a)).sum(axis=(-1, -2))
+    cov, vx, vy = N * sxy - sx * sy, N * sxx - sx * sx, N * syy - sy * sy
+    ok = (vx != 0) & (vy != 0)
+    c = cov.astype(np.float64)
+    den = np.where(ok, vx.astype(np.float64) * vy.astype(np.float64), 1.0)
+    return np.where(ok, (c * c) / den, np.nan)
