@@ -107,6 +107,29 @@ extern "C" int emu_decompress(const uint8_t *in, uint64_t n, uint8_t *out, uint6
     return st;
 }
 
+// The device entries vcfc_decode_records_device / vcfc_decode_selected_device
+// (select = null: every record), step for step as csrc/vcfc_api.cpp takes
+// them: the plan (exact or light), then the write.
+extern "C" int emu_decode_device(const uint8_t *recs, uint64_t in_bytes, const uint64_t *rec, const uint8_t *select,
+                                 uint64_t n, uint64_t S, uint8_t *out, uint64_t out_cap, uint64_t *line_off,
+                                 uint64_t *err, int exact) {
+    const VcfcDecodeLayout L = vcfc_decode_workspace_layout(n);
+    std::vector<uint8_t> ws(L.total + 64, 0xCD);
+    HostInput in(recs, in_bytes);
+    VcfcDecodeArgs a;
+    a.in = in.p; a.n_bytes = in_bytes; a.rec_start = rec; a.select = select; a.n = n; a.S = S;
+    a.out = out; a.out_cap = out_cap; a.line_off = line_off;
+    a.st = reinterpret_cast<uint32_t *>(ws.data() + L.st);
+    a.line_size = reinterpret_cast<uint32_t *>(ws.data() + L.line_size);
+    a.end = reinterpret_cast<uint64_t *>(ws.data() + L.end);
+    a.seq_list = reinterpret_cast<uint32_t *>(ws.data() + L.seq_list);
+    a.seq_count = reinterpret_cast<uint32_t *>(ws.data() + L.seq_count);
+    a.err = err;
+    a.partials = reinterpret_cast<uint64_t *>(ws.data() + L.partials);
+    if (vcfc_decode_plan(a, exact != 0, nullptr) != hipSuccess) return 3;
+    return vcfc_decode_write(a, 0, n, nullptr) == hipSuccess ? 0 : 3;
+}
+
 // Range query through the product driver (vcfc_dec::query_section).
 extern "C" int emu_query(const uint8_t *in, uint64_t n, const uint8_t *ref, uint64_t ref_len, int has_range,
                          uint64_t qstart, uint64_t qend, uint8_t *out, uint64_t cap, uint64_t *out_len,

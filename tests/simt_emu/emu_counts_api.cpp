@@ -64,8 +64,7 @@ extern "C" int emu_counts_file(const uint8_t *in, uint64_t n, int has_query, con
 // argument) on records [rec[0], rec[n])
 extern "C" int emu_counts_device(const uint8_t *recs, const uint64_t *rec, const uint8_t *select, uint64_t n, uint64_t S,
                                  uint32_t *variant, uint64_t *sample, uint8_t *ws, uint64_t ws_bytes, uint64_t *err) {
-    std::vector<uint8_t> in(recs, recs + (n && rec ? rec[n] : 0));
-    in.resize(in.size() + 64, 0xCD);
-    return vcfc_cnt::counts_device(recs ? in.data() : nullptr, n && rec ? rec[n] : 0, rec, select, n, S, variant, sample, ws,
+    HostInput in(recs, n && rec ? rec[n] : 0);
+    return vcfc_cnt::counts_device(recs ? in.p : nullptr, n && rec ? rec[n] : 0, rec, select, n, S, variant, sample, ws,
                                    ws_bytes, err, nullptr);
 }

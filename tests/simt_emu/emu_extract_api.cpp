@@ -68,8 +68,7 @@ extern "C" int emu_extract_device(const uint8_t *recs, const uint64_t *rec, cons
     std::vector<uint32_t> csort, rank;
     if (vcfc_ext::device_columns(cols, K, S, csort, rank)) return vcfc_ext::ST_E_ARG;
     std::vector<uint8_t> ws(vcfc_extract_workspace_layout(n, csort.size()).total + 64, 0xCD);
-    std::vector<uint8_t> in(recs, recs + (n ? rec[n] : 0));
-    in.resize(in.size() + 64, 0xCD);
-    return vcfc_sub::records_device(vcfc_ext::EXTRACT, in.data(), n ? rec[n] : 0, rec, select, n, S, csort, rank, out, out_cap,
+    HostInput in(recs, n ? rec[n] : 0);
+    return vcfc_sub::records_device(vcfc_ext::EXTRACT, in.p, n ? rec[n] : 0, rec, select, n, S, csort, rank, out, out_cap,
                                     rec_off, ws.data(), ws.size(), err, nullptr);
 }

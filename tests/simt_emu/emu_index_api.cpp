@@ -16,24 +16,6 @@
 #include "host_buffers.h"
 
 namespace {
-// A copy of [p, p + n) that ends at a page with no access: a read past the
-// last record's end faults.
-struct Guarded {
-    uint8_t *map = nullptr, *p = nullptr;
-    size_t len = 0;
-    Guarded(const uint8_t *src, uint64_t n) {
-        const size_t pg = (size_t)sysconf(_SC_PAGESIZE);
-        const size_t body = (n + pg - 1) / pg * pg;
-        len = body + pg;
-        map = static_cast<uint8_t *>(mmap(nullptr, len, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0));
-        if (map == MAP_FAILED) abort();
-        mprotect(map + body, pg, PROT_NONE);
-        p = map + body - n;
-        if (n) memcpy(p, src, n);
-    }
-    ~Guarded() { munmap(map, len); }
-};
-
 // reads of the queried file, logged as (offset, bytes) pairs
 struct LogReader : vcfc_idx::Reader {
     const uint8_t *p;
@@ -90,7 +72,7 @@ extern "C" int emu_index_device(const uint8_t *recs, const uint64_t *rec, uint64
                                 uint8_t *entries, uint64_t entries_cap, uint64_t *words) {
     const VcfcIndexLayout L = vcfc_index_workspace_layout(n);
     std::vector<uint8_t> ws(L.total + 64, 0xCD);
-    Guarded g(recs, n ? rec[n] : 0);
+    HostInput g(recs, n ? rec[n] : 0, true);   // behind a guard page (host_buffers.h)
     words[0] = words[1] = words[2] = 0xCDCDCDCDCDCDCDCDull;
     return (int)vcfc_index_build(g.p, rec, n, base, E, entries, entries_cap, words + 1, words + 2, ws.data(), L, words,
                                  nullptr);
@@ -99,7 +81,7 @@ extern "C" int emu_index_device(const uint8_t *recs, const uint64_t *rec, uint64
 // vcfc_index_span on records behind a guard page
 extern "C" int emu_record_span(const uint8_t *recs, const uint64_t *rec, uint64_t n, uint8_t *ref_idx, uint64_t *pos,
                                uint64_t *end, uint64_t *err) {
-    Guarded g(recs, n ? rec[n] : 0);
+    HostInput g(recs, n ? rec[n] : 0, true);   // behind a guard page (host_buffers.h)
     return (int)vcfc_index_span(g.p, rec, n, ref_idx, pos, end, err, nullptr);
 }
 

@@ -82,8 +82,7 @@ extern "C" int emu_ld_window_device(const uint8_t *recs, const uint64_t *rec, co
                                     uint64_t ws_bytes, uint64_t *err) {
     if (n >= (1ull << 32))   // (refused before rec[n] is looked at: nothing to copy)
         return vcfc_ld::window_device(recs, 0, rec, select, n, S, W, tables, pairs_cap, row_of, ws, ws_bytes, err, nullptr);
-    std::vector<uint8_t> in(recs, recs + (n && rec ? rec[n] : 0));
-    in.resize(in.size() + 64, 0xCD);
-    return vcfc_ld::window_device(recs ? in.data() : nullptr, n && rec ? rec[n] : 0, rec, select, n, S, W, tables, pairs_cap,
+    HostInput in(recs, n && rec ? rec[n] : 0);
+    return vcfc_ld::window_device(recs ? in.p : nullptr, n && rec ? rec[n] : 0, rec, select, n, S, W, tables, pairs_cap,
                                   row_of, ws, ws_bytes, err, nullptr);
 }

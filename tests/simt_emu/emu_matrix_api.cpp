@@ -88,8 +88,7 @@ extern "C" int emu_matrix_device(const uint8_t *recs, const uint64_t *rec, const
     if (n >= (1ull << 32))   // (refused before rec[n] is looked at: nothing to copy)
         return vcfc_gm::matrix_device(recs, 0, rec, select, n, S, layout, out, out_cap, row_stride, row_of, ws, ws_bytes, err,
                                       nullptr);
-    std::vector<uint8_t> in(recs, recs + (n && rec ? rec[n] : 0));
-    in.resize(in.size() + 64, 0xCD);
-    return vcfc_gm::matrix_device(recs ? in.data() : nullptr, n && rec ? rec[n] : 0, rec, select, n, S, layout, out, out_cap,
+    HostInput in(recs, n && rec ? rec[n] : 0);
+    return vcfc_gm::matrix_device(recs ? in.p : nullptr, n && rec ? rec[n] : 0, rec, select, n, S, layout, out, out_cap,
                                   row_stride, row_of, ws, ws_bytes, err, nullptr);
 }

@@ -43,20 +43,18 @@ extern "C" int emu_regions_upload(const uint8_t *table, uint64_t bytes, void *ws
 // argument) on records [rec[0], rec[n])
 extern "C" int emu_regions_match(const uint8_t *recs, const uint64_t *rec, uint64_t n, const void *ws, uint64_t ws_bytes,
                                  uint8_t *flag, uint64_t *err) {
-    std::vector<uint8_t> in(recs, recs + (n ? rec[n] : 0));
-    in.resize(in.size() + 64, 0xCD);
-    return vcfc_reg::regions_match_device(in.data(), rec, n, ws, ws_bytes, flag, err, nullptr);
+    HostInput in(recs, n ? rec[n] : 0);
+    return vcfc_reg::regions_match_device(in.p, rec, n, ws, ws_bytes, flag, err, nullptr);
 }
 
 // the one-region match (the C ABI's vcfc_query_match_device) on the same records
 extern "C" int emu_regions_query_match(const uint8_t *recs, const uint64_t *rec, uint64_t n, const uint8_t *ref,
                                        uint64_t ref_len, int has_range, uint64_t start, uint64_t end, uint8_t *flag,
                                        uint64_t *err) {
-    std::vector<uint8_t> in(recs, recs + (n ? rec[n] : 0));
-    in.resize(in.size() + 64, 0xCD);
+    HostInput in(recs, n ? rec[n] : 0);
     VcfcQuery q;
     q.ref = ref; q.ref_len = (uint32_t)ref_len; q.has_range = has_range ? 1u : 0u; q.start = start; q.end = end;
-    return vcfc_query_match(in.data(), rec, n, q, flag, err, nullptr) == hipSuccess ? 0 : vcfc_reg::ST_E_HIP;
+    return vcfc_query_match(in.p, rec, n, q, flag, err, nullptr) == hipSuccess ? 0 : vcfc_reg::ST_E_HIP;
 }
 
 // query-regions over a whole .vcfc (the C ABI's control flow)

@@ -20,24 +20,6 @@
 #include "host_buffers.h"
 
 namespace {
-// A copy of [p, p + n) that ends at a page with no access: a read past the
-// last record's end faults.
-struct Guarded {
-    uint8_t *map = nullptr, *p = nullptr;
-    size_t len = 0;
-    Guarded(const uint8_t *src, uint64_t n) {
-        const size_t pg = (size_t)sysconf(_SC_PAGESIZE);
-        const size_t body = (n + pg - 1) / pg * pg;
-        len = body + pg;
-        map = static_cast<uint8_t *>(mmap(nullptr, len, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0));
-        if (map == MAP_FAILED) abort();
-        mprotect(map + body, pg, PROT_NONE);
-        p = map + body - n;
-        if (n) memcpy(p, src, n);
-    }
-    ~Guarded() { munmap(map, len); }
-};
-
 constexpr uint64_t BLK = 4096;
 // a sparse file of 4 KiB blocks: written blocks are data, the rest are holes
 struct BlockFile : vcfc_spx::Writer, vcfc_spx::IndexFile {
@@ -152,7 +134,7 @@ extern "C" int emu_spx_device(const uint8_t *recs, const uint64_t *rec, uint64_t
                               uint64_t *file_off, uint64_t *words) {
     const VcfcSparseIndexLayout L = vcfc_sparse_index_workspace_layout(n);
     std::vector<uint8_t> ws(L.total + 64, 0xCD);
-    Guarded g(recs, n ? rec[n] : 0);
+    HostInput g(recs, n ? rec[n] : 0, true);   // behind a guard page (host_buffers.h)
     for (int k = 0; k < 5; k++) words[k] = 0xCDCDCDCDCDCDCDCDull;
     return (int)vcfc_sparse_index_build(g.p, rec, n, base, entries, file_off, words + 1, words + 2, ws.data(), L, words,
                                         nullptr);
@@ -161,8 +143,30 @@ extern "C" int emu_spx_device(const uint8_t *recs, const uint64_t *rec, uint64_t
 // vcfc_sparse_index_span on records behind a guard page
 extern "C" int emu_spx_span(const uint8_t *recs, const uint64_t *rec, uint64_t n, int walk, uint8_t *ref_idx,
                             uint64_t *pos, uint64_t *err) {
-    Guarded g(recs, n ? rec[n] : 0);
+    HostInput g(recs, n ? rec[n] : 0, true);   // behind a guard page (host_buffers.h)
     return (int)vcfc_sparse_index_span(g.p, rec, n, walk, ref_idx, pos, err, nullptr);
+}
+
+// The device entry vcfc_decode_sizes_device, step for step as csrc/vcfc_api.cpp
+// takes it: the exact plan without the write, then the gap fields.
+extern "C" int emu_decode_sizes(const uint8_t *recs, uint64_t in_bytes, const uint64_t *rec, uint64_t n, uint64_t S,
+                                uint64_t *line_off, uint64_t *pos_off, uint32_t *pos_len, uint64_t *ccount,
+                                uint64_t *err) {
+    const VcfcDecodeLayout L = vcfc_decode_workspace_layout(n);
+    std::vector<uint8_t> ws(L.total + 64, 0xCD);
+    HostInput in(recs, in_bytes);
+    VcfcDecodeArgs a;
+    a.in = in.p; a.n_bytes = in_bytes; a.rec_start = rec; a.select = nullptr; a.n = n; a.S = S;
+    a.out = nullptr; a.out_cap = 0; a.line_off = line_off;
+    a.st = reinterpret_cast<uint32_t *>(ws.data() + L.st);
+    a.line_size = reinterpret_cast<uint32_t *>(ws.data() + L.line_size);
+    a.end = reinterpret_cast<uint64_t *>(ws.data() + L.end);
+    a.seq_list = reinterpret_cast<uint32_t *>(ws.data() + L.seq_list);
+    a.seq_count = reinterpret_cast<uint32_t *>(ws.data() + L.seq_count);
+    a.err = err;
+    a.partials = reinterpret_cast<uint64_t *>(ws.data() + L.partials);
+    if (vcfc_decode_plan(a, true, nullptr) != hipSuccess) return 3;
+    return vcfc_gap_fields(in.p, rec, n, S, pos_off, pos_len, ccount, err, nullptr) == hipSuccess ? 0 : 3;
 }
 
 // vcfc_spx::gap_analysis over a whole .vcfc: the text of start-positions.txt

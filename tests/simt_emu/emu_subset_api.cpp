@@ -71,9 +71,8 @@ extern "C" int emu_subset_device(const uint8_t *recs, const uint64_t *rec, const
     std::vector<uint32_t> csort, rank;
     if (vcfc_sub::sort_columns(cols, K, S, csort, rank)) return vcfc_sub::ST_E_ARG;
     std::vector<uint8_t> ws(vcfc_subset_workspace_layout(n, K).total + 64, 0xCD);
-    std::vector<uint8_t> in(recs, recs + (n ? rec[n] : 0));
-    in.resize(in.size() + 64, 0xCD);
-    return vcfc_sub::records_device(vcfc_sub::SUBSET, in.data(), n ? rec[n] : 0, rec, select, n, S, csort, rank, out, out_cap,
+    HostInput in(recs, n ? rec[n] : 0);
+    return vcfc_sub::records_device(vcfc_sub::SUBSET, in.p, n ? rec[n] : 0, rec, select, n, S, csort, rank, out, out_cap,
                                     line_off, ws.data(), ws.size(), err, nullptr);
 }
 
