@@ -789,6 +789,73 @@ int vcfc_ld_window_file(vcfc_ctx *ctx, const char *in_vcfc, const char *out_tsv,
 int vcfc_ld_window_regions_file(vcfc_ctx *ctx, const char *in_vcfc, const char *out_tsv, uint64_t window, double min_r2,
                                 const uint8_t *table, uint64_t table_bytes);
 
+/* ---- kinship: kinship, kinship-regions (no reference action:
+ * the oracle is a plain restatement over the .bed rows) ------------------------
+ * Pairwise genotype tables of the samples over the rows of the genotype
+ * matrix.  The rows are vcfc_genotype_matrix_*'s (every record, or the records
+ * a region or a region table matches; the same regular-record and stop rules);
+ * the genotype of sample s in a row is its VCFC_GM_BED code: 11 -> 0, 10 -> 1,
+ * 00 -> 2, 01 -> missing; pad bits are never counted.  For samples i, j,
+ * t[i][j][3 a + b] = the rows with g_i = a and g_j = b, both called: nine
+ * uint32 at (i * samples + j) * 9, the full square (t[j][i] is the transpose,
+ * t[i][i] is diagonal: the sample's own called genotype counts).  Statistics
+ * of a table, exact in int64: N = sum t, IBS0 = t[2] + t[6], IBS2 = t[0] + t[4]
+ * + t[8], IBS1 = N - IBS0 - IBS2, HH = t[4], HET_A = t[3] + t[4] + t[5], HET_B =
+ * t[1] + t[4] + t[7], m = min(HET_A, HET_B); DST = (double)(2 IBS2 + IBS1) /
+ * (double)(2 N), undefined for N == 0; KINSHIP (KING-robust, between families)
+ * = (double)(2 HH - 4 IBS0 + 2 m - HET_A - HET_B) / (double)(4 m), undefined for
+ * m == 0.  The device delivers the integers only.
+ *
+ * vcfc_kin_tables_device: the pair step on .bed rows the caller holds (row r at
+ * d_bed + r * row_stride, any row_stride >= row_bytes, any alignment; the
+ * aligned 4-byte words that hold a row's bytes are read).  d_tables: 4-byte
+ * aligned, room for tables_cap >= samples^2 tables; d_ws: 16-byte aligned (the
+ * bit planes in it are read 16 bytes at a time; hipMalloc gives 256), in both
+ * device entries; accumulate != 0 adds to
+ * what it holds (tables are additive over rows), else the square is stored.
+ * *d_err = ~0.  vcfc_kin_records_device: the composed call on device-resident
+ * records, arguments as vcfc_genotype_matrix_device's: that call (layout
+ * VCFC_GM_BED) writes the rows into the workspace, then bit planes, then
+ * pairs, all enqueued on `stream` with no host synchronisation and per-call
+ * state reset by a kernel (capturable).  d_row_of as there (n + 1 words).
+ * *d_err is the matrix call's word: with (i << 8 | 3), a selected record that
+ * is not regular, the tables are exactly those of the rows [0, d_row_of[i])
+ * before it.  VCFC_E_ARG, nothing written: samples == 0 or >= 2^30, n (n_rows)
+ * >= 2^32, row_stride < row_bytes, tables_cap < samples^2, a null d_tables,
+ * d_row_of, d_ws or d_err, ws_bytes below vcfc_kin_workspace_size(n, samples). */
+uint64_t vcfc_kin_workspace_size(uint64_t n_records, uint64_t samples);
+int vcfc_kin_tables_device(const uint8_t *d_bed, uint64_t n_rows, uint64_t row_stride, uint64_t samples, uint32_t *d_tables,
+                           uint64_t tables_cap, int accumulate, void *d_ws, uint64_t ws_bytes, uint64_t *d_err, void *stream);
+int vcfc_kin_records_device(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_rec_start, const uint8_t *d_select,
+                            uint64_t n, uint64_t samples, uint32_t *d_tables, uint64_t tables_cap, int accumulate,
+                            uint64_t *d_row_of, void *d_ws, uint64_t ws_bytes, uint64_t *d_err, void *stream);
+/* A whole .vcfc in host memory, in batches of records that add into one
+ * square.  rec_index[0, *n_rows) = the rows' records' file indices (room for
+ * rows_cap), tables = the *n_samples^2 tables (room for tables_cap tables).
+ * VCFC_E_NOSPACE if either is short: *n_rows and *n_samples then give the
+ * sizes.  On VCFC_E_FORMAT the result is exactly the square of the rows before
+ * the failing record, as if the file ended there, and *err_record is its file
+ * index (the record count where hopping stopped short).  The _regions entry
+ * takes a built table (vcfc_regions_build). */
+int vcfc_kinship_buffer(vcfc_ctx *ctx, const uint8_t *in, uint64_t in_bytes, int has_query, const char *ref, uint64_t ref_len,
+                        int has_range, uint64_t start, uint64_t end, uint64_t *rec_index, uint64_t rows_cap, uint32_t *tables,
+                        uint64_t tables_cap, uint64_t *n_rows, uint64_t *n_samples, uint64_t *err_record);
+int vcfc_kinship_regions_buffer(vcfc_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const uint8_t *table,
+                                uint64_t table_bytes, uint64_t *rec_index, uint64_t rows_cap, uint32_t *tables,
+                                uint64_t tables_cap, uint64_t *n_rows, uint64_t *n_samples, uint64_t *err_record);
+/* out_tsv is opened (created, truncated) before the input is parsed.  The line
+ * "#ID_A\tID_B\tN\tIBS0\tIBS1\tIBS2\tHETHET\tHET_A\tHET_B\tDST\tKINSHIP\n",
+ * then one line per written pair i < j, i ascending, then j: the two sample
+ * names verbatim from the '#CHROM' line, the seven integers in decimal, DST and
+ * KINSHIP as printf's %.6g or "nan" where undefined.  has_min != 0: a pair is
+ * written iff its kinship is defined and >= min_kinship; else every pair.  On
+ * VCFC_E_FORMAT past the header the pairs of the rows before the failing
+ * record are written; a header that is refused leaves the file empty. */
+int vcfc_kinship_file(vcfc_ctx *ctx, const char *in_vcfc, const char *out_tsv, int has_min, double min_kinship,
+                      int has_query, const char *ref, uint64_t ref_len, int has_range, uint64_t start, uint64_t end);
+int vcfc_kinship_regions_file(vcfc_ctx *ctx, const char *in_vcfc, const char *out_tsv, int has_min, double min_kinship,
+                              const uint8_t *table, uint64_t table_bytes);
+
 /* ---- extract: extract-samples, extract-regions (no reference
  * action: the oracle is the reference's own compress of the cut text) ----------
  * A sample / region subset of a .vcfc, written as a .vcfc; no record becomes

@@ -17,8 +17,10 @@
 // <out> <names> [<query>]` and `main extract-regions <in> <out> <regions>
 // [<names>]`, and the pairwise LD of nearby rows: `main
 // ld-window <in> <out.tsv> <window> <min-r2> [<query>]` and `main
-// ld-window-regions <in> <out.tsv> <window> <min-r2> <regions>`
-// (DESIGN.md §4l).  Data lines are
+// ld-window-regions <in> <out.tsv> <window> <min-r2> <regions>`, and the
+// pairwise tables, IBS and kinship of the samples: `main
+// kinship <in> <out.tsv> <min-kinship|all> [<query>]` and `main
+// kinship-regions <in> <out.tsv> <min-kinship|all> <regions>`.  Data lines are
 // encoded on the GPU through libvcfc.so.  Error messages mirror the
 // reference's exceptions (which terminate the reference process).
 #include <cerrno>
@@ -53,7 +55,9 @@ static int usage() {
                     "./main extract-samples <input_file> <output_file> <name>[,<name>...] [<ref>[:<start>-<end>]]\n"
                     "./main extract-regions <input_file> <output_file> <regions-file> [<name>[,<name>...]]\n"
                     "./main ld-window <input_file> <out.tsv> <window> <min-r2> [<ref>[:<start>-<end>]]\n"
-                    "./main ld-window-regions <input_file> <out.tsv> <window> <min-r2> <regions-file>\n");
+                    "./main ld-window-regions <input_file> <out.tsv> <window> <min-r2> <regions-file>\n"
+                    "./main kinship <input_file> <out.tsv> <min-kinship|all> [<ref>[:<start>-<end>]]\n"
+                    "./main kinship-regions <input_file> <out.tsv> <min-kinship|all> <regions-file>\n");
     return 1;
 }
 
@@ -754,6 +758,59 @@ int main(int argc, char **argv) {
         }
         if (st != VCFC_OK) {
             fprintf(stderr, "Error in ld-window of file: %s\n", vcfc_strerror(st));
+            return 1;
+        }
+        return 0;
+    }
+    if (action == "kinship" || action == "kinship-regions") {
+        // no reference counterpart: genotype tables, IBS and KING kinship of every pair of samples
+        const bool regions = action == "kinship-regions";
+        if (argc < (regions ? 6 : 5)) return usage();
+        const bool all = std::string(argv[4]) == "all";
+        char *re = nullptr;
+        errno = 0;
+        const double min_kinship = all ? 0.0 : strtod(argv[4], &re);
+        if (!all && (errno || !*argv[4] || *re || min_kinship != min_kinship)) return usage();
+        std::vector<uint8_t> table;
+        if (regions && load_regions(argv[5], table)) return 1;   // before the input is opened
+        if (!file_exists(argv[2])) printf("Input file does not exist: %s\n", argv[2]);
+        if (std::string(argv[2]) == argv[3]) {
+            fprintf(stderr, "terminate called after throwing an instance of 'std::runtime_error'\n"
+                            "  what():  input and output file are the same\n");
+            return 134;
+        }
+        const bool query = !regions && argc > 5;
+        const std::string q(query ? argv[5] : "");
+        uint64_t ref_len = 0, start = 0, end = 0;
+        int has_range = 0;
+        if (query) {
+            const int pq = vcfc_parse_query(q.data(), q.size(), &ref_len, &has_range, &start, &end);
+            if (pq != 0) {
+                const size_t colon = q.find(':'), dash = q.find('-', colon + 1);
+                if (pq == 1) printf("Query must contain a dash character: <ref>:<start>-<end>\n");
+                else if (pq == 2) printf("Failed to parse int from start position: %s\n", q.substr(colon + 1, dash - colon - 1).c_str());
+                else printf("Failed to parse int from end position: %s\n", q.substr(dash + 1).c_str());
+                printf("Failed to parse query string: %s\n", q.c_str());
+                return 1;
+            }
+        }
+        vcfc_ctx *ctx = nullptr;
+        int st = vcfc_ctx_create(0, &ctx);
+        if (st != VCFC_OK) {
+            fprintf(stderr, "vcfc: %s\n", vcfc_strerror(st));
+            return 1;
+        }
+        fflush(stdout);
+        if (regions) st = vcfc_kinship_regions_file(ctx, argv[2], argv[3], all ? 0 : 1, min_kinship, table.data(), table.size());
+        else st = vcfc_kinship_file(ctx, argv[2], argv[3], all ? 0 : 1, min_kinship, query ? 1 : 0, q.data(), ref_len, has_range, start, end);
+        vcfc_ctx_destroy(ctx);
+        if (st == VCFC_E_FORMAT) {
+            fprintf(stderr, "terminate called after throwing an instance of 'VcfValidationError'\n"
+                            "  what():  %s\n", vcfc_strerror(st));
+            return 134;
+        }
+        if (st != VCFC_OK) {
+            fprintf(stderr, "Error in kinship of file: %s\n", vcfc_strerror(st));
             return 1;
         }
         return 0;

@@ -27,6 +27,7 @@
 #include "vcfc_extract_driver.h"
 #include "vcfc_counts_driver.h"
 #include "vcfc_ld_driver.h"
+#include "vcfc_kin_driver.h"
 #include "vcfc_matrix_driver.h"
 #include "vcfc_regions_driver.h"
 
@@ -1907,6 +1908,115 @@ int vcfc_ld_window_regions_file(vcfc_ctx *c, const char *in_path, const char *ou
     return ld_to_file(c, in_path, out_tsv, window, min_r2,
                       [&](const uint8_t *p, uint64_t pn, vcfc_dec::Buffers &B, vcfc_ld::Result &R, uint64_t *data_off,
                           uint64_t *S) { return vcfc_ld::window_file(p, pn, window, &match, B, c->stream, R, data_off, S); });
+}
+
+// ---- kinship; driver in vcfc_kin_driver.h ------------------------
+
+uint64_t vcfc_kin_workspace_size(uint64_t n_records, uint64_t samples) {
+    return vcfc_kin_workspace_layout(n_records, samples).total;
+}
+
+int vcfc_kin_tables_device(const uint8_t *d_bed, uint64_t n_rows, uint64_t row_stride, uint64_t samples, uint32_t *d_tables,
+                           uint64_t tables_cap, int accumulate, void *d_ws, uint64_t ws_bytes, uint64_t *d_err, void *stream) {
+    return vcfc_kin::tables_device(d_bed, n_rows, row_stride, samples, d_tables, tables_cap, accumulate, d_ws, ws_bytes, d_err,
+                                   static_cast<hipStream_t>(stream));
+}
+
+int vcfc_kin_records_device(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_rec_start, const uint8_t *d_select,
+                            uint64_t n, uint64_t samples, uint32_t *d_tables, uint64_t tables_cap, int accumulate,
+                            uint64_t *d_row_of, void *d_ws, uint64_t ws_bytes, uint64_t *d_err, void *stream) {
+    return vcfc_kin::records_device(d_in, in_bytes, d_rec_start, d_select, n, samples, d_tables, tables_cap, accumulate, d_row_of,
+                                    d_ws, ws_bytes, d_err, static_cast<hipStream_t>(stream));
+}
+
+namespace {
+// run(in, n, B, R, &data_off, &S): the square of a .vcfc by one of the two match steps
+using KinRun = std::function<int(const uint8_t *, uint64_t, vcfc_dec::Buffers &, vcfc_kin::Result &, uint64_t *, uint64_t *)>;
+
+// what the two kinship buffer entries hand back
+int kin_to_caller(vcfc_ctx *c, const uint8_t *in, uint64_t n, uint64_t *rec_index, uint64_t rows_cap, uint32_t *tables,
+                  uint64_t tables_cap, uint64_t *n_rows, uint64_t *n_samples, uint64_t *err_record, const KinRun &run) {
+    if (!c || (!in && n) || (!rec_index && rows_cap) || (!tables && tables_cap) || !n_rows || !n_samples || !err_record)
+        return VCFC_E_ARG;
+    *n_rows = *n_samples = 0;
+    *err_record = ~0ull;
+    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
+    vcfc_kin::Result R;
+    uint64_t data_off = 0, S = 0;
+    CtxDecodeBuffers B(c);
+    const int st = run(in, n, B, R, &data_off, &S);
+    if (st != VCFC_OK && st != VCFC_E_FORMAT) return st;
+    *n_rows = R.index.size();
+    *n_samples = S;
+    *err_record = R.err_record;
+    if (*n_rows > rows_cap || R.tables.size() / 9 > tables_cap) return VCFC_E_NOSPACE;
+    if (*n_rows) memcpy(rec_index, R.index.data(), 8 * R.index.size());
+    if (!R.tables.empty()) memcpy(tables, R.tables.data(), 4 * R.tables.size());
+    return st;
+}
+
+// the text file of a kinship entry
+int kin_to_file(vcfc_ctx *c, const char *in_path, const char *out_path, int has_min, double min_kinship, const KinRun &run) {
+    const int fd = open(out_path, O_CREAT | O_TRUNC | O_WRONLY, 0644);
+    if (fd < 0) return VCFC_E_IO;
+    MappedFile f;
+    int st = f.open_ro(in_path);
+    if (!st) {
+        vcfc_kin::Result R;
+        uint64_t data_off = 0, S = 0;
+        CtxDecodeBuffers B(c);
+        st = run(f.p, f.n, B, R, &data_off, &S);
+        if (data_off && S && !R.tables.empty() && (st == VCFC_OK || st == VCFC_E_FORMAT)) {   // past the header
+            std::vector<uint8_t> text;
+            vcfc_kin::render_tsv(f.p, data_off, S, R, has_min != 0, min_kinship, text);
+            if (write_all_at(fd, text.data(), text.size(), 0)) st = VCFC_E_IO;
+        }
+    }
+    if (close(fd) != 0 && !st) st = VCFC_E_IO;
+    return st;
+}
+}  // namespace
+
+int vcfc_kinship_buffer(vcfc_ctx *c, const uint8_t *in, uint64_t n, int has_query, const char *ref, uint64_t ref_len,
+                        int has_range, uint64_t start, uint64_t end, uint64_t *rec_index, uint64_t rows_cap, uint32_t *tables,
+                        uint64_t tables_cap, uint64_t *n_rows, uint64_t *n_samples, uint64_t *err_record) {
+    if (has_query && !ref && ref_len) return VCFC_E_ARG;
+    const vcfc_kin::Query q{reinterpret_cast<const uint8_t *>(ref), ref_len, has_range, start, end};
+    return kin_to_caller(c, in, n, rec_index, rows_cap, tables, tables_cap, n_rows, n_samples, err_record,
+                         [&](const uint8_t *p, uint64_t pn, vcfc_dec::Buffers &B, vcfc_kin::Result &R, uint64_t *data_off,
+                             uint64_t *S) { return vcfc_kin::kin_file(p, pn, has_query ? &q : nullptr, B, c->stream, R, data_off, S); });
+}
+
+int vcfc_kinship_regions_buffer(vcfc_ctx *c, const uint8_t *in, uint64_t n, const uint8_t *table, uint64_t table_bytes,
+                                uint64_t *rec_index, uint64_t rows_cap, uint32_t *tables, uint64_t tables_cap, uint64_t *n_rows,
+                                uint64_t *n_samples, uint64_t *err_record) {
+    if (!vcfc_reg::regions_validate(table, table_bytes)) return VCFC_E_ARG;
+    const uint8_t *d_table = nullptr;
+    const vcfc_dec::MatchStep match = vcfc_reg::regions_step(table, table_bytes, &d_table);
+    return kin_to_caller(c, in, n, rec_index, rows_cap, tables, tables_cap, n_rows, n_samples, err_record,
+                         [&](const uint8_t *p, uint64_t pn, vcfc_dec::Buffers &B, vcfc_kin::Result &R, uint64_t *data_off,
+                             uint64_t *S) { return vcfc_kin::kin_file(p, pn, &match, B, c->stream, R, data_off, S); });
+}
+
+int vcfc_kinship_file(vcfc_ctx *c, const char *in_path, const char *out_tsv, int has_min, double min_kinship, int has_query,
+                      const char *ref, uint64_t ref_len, int has_range, uint64_t start, uint64_t end) {
+    if (!c || !in_path || !out_tsv || (has_query && !ref && ref_len)) return VCFC_E_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
+    const vcfc_kin::Query q{reinterpret_cast<const uint8_t *>(ref), ref_len, has_range, start, end};
+    return kin_to_file(c, in_path, out_tsv, has_min, min_kinship,
+                       [&](const uint8_t *p, uint64_t pn, vcfc_dec::Buffers &B, vcfc_kin::Result &R, uint64_t *data_off,
+                           uint64_t *S) { return vcfc_kin::kin_file(p, pn, has_query ? &q : nullptr, B, c->stream, R, data_off, S); });
+}
+
+int vcfc_kinship_regions_file(vcfc_ctx *c, const char *in_path, const char *out_tsv, int has_min, double min_kinship,
+                              const uint8_t *table, uint64_t table_bytes) {
+    if (!c || !in_path || !out_tsv || !vcfc_reg::regions_validate(table, table_bytes)) return VCFC_E_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return VCFC_E_HIP;
+    const uint8_t *d_table = nullptr;
+    const vcfc_dec::MatchStep match = vcfc_reg::regions_step(table, table_bytes, &d_table);
+    return kin_to_file(c, in_path, out_tsv, has_min, min_kinship,
+                       [&](const uint8_t *p, uint64_t pn, vcfc_dec::Buffers &B, vcfc_kin::Result &R, uint64_t *data_off,
+                           uint64_t *S) { return vcfc_kin::kin_file(p, pn, &match, B, c->stream, R, data_off, S); });
 }
 
 int vcfc_query_match_device(const uint8_t *d_in, const uint64_t *d_rec_start, uint64_t n, const uint8_t *d_ref,

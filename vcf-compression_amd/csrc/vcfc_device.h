@@ -426,6 +426,36 @@ VcfcLdLayout vcfc_ld_workspace_layout(uint64_t n, uint64_t S);
 hipError_t vcfc_ld_run(const VcfcLdArgs &a, hipStream_t s);
 
 // ---------------------------------------------------------------------------
+// Kinship (vcfc_kin.hip): the 3 x 3 genotype table of every
+// pair of samples over the .bed rows, by AND + population count over three
+// sample-major bit planes (H: g = 1, B: g = 2, V: called; 32 variants a word).
+#define VCFC_KIN_TILE_SAMPLES 32u    // a block of k_kin_pairs owns a tile of 32 x 32 sample pairs
+#define VCFC_KIN_CHUNK_WORDS 16u     // variant words of every staged sample in LDS at a time
+#define VCFC_KIN_PLANE_ROWS 256u     // variant rows a block of k_kin_planes covers (32 bytes a sample and plane)
+struct VcfcKinArgs {
+    const uint8_t *bed;         // .bed rows, row r at bed + r * row_stride (any alignment)
+    uint64_t row_stride;
+    uint64_t n;                 // rows at most (the workspace and the grids are sized by it)
+    const uint64_t *row_of;     // nullptr: n rows; else the matrix call's row_of (n + 1 words): row_of[n] rows,
+                                //   cut to row_of[k] where err holds (k << 8 | 3)
+    uint64_t S;
+    uint32_t *tables;           // table (i, j) at tables + (i * S + j) * 9
+    int accumulate;             // != 0: add to what tables holds
+    uint64_t *err;
+    bool own_err;               // the call resets err itself (no matrix call before it)
+    // workspace (vcfc_kin_workspace_layout)
+    uint64_t *state;            // [0] the rows that are counted
+    uint32_t *planes;           // sample s, plane p at planes + (3 s + p) * row_words
+    uint64_t row_words;         // a multiple of 4 (16 bytes); every bit at or past the row count is 0
+};
+struct VcfcKinLayout {
+    uint64_t state, planes, bed, bed_stride, row_words, matrix, total;
+};
+VcfcKinLayout vcfc_kin_workspace_layout(uint64_t n, uint64_t S);
+// reset, planes, pairs: enqueued on s, no host synchronisation
+hipError_t vcfc_kin_run(const VcfcKinArgs &a, hipStream_t s);
+
+// ---------------------------------------------------------------------------
 // Range query (vcfc_decode.hip; reference query_compressed_file,
 // src/main.cpp:3777-3929).  `ref` is device memory.
 struct VcfcQuery {

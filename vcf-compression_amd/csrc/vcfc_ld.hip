@@ -30,6 +30,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <vcfc_wave.h>   // angle brackets: tests/simt_emu shadows it
+#include "vcfc_bed_planes.h"
 #include "vcfc_device.h"
 
 namespace {
@@ -61,19 +62,8 @@ __global__ __launch_bounds__(256) void k_ld_cap(VcfcLdArgs a) {
     if (a.row_of[i] >= a.state[1]) atomicMin((unsigned long long *)a.err, (unsigned long long)((i << 8) | 0xFFull));
 }
 
-// bits 0, 2, 4, ... of x as the low 32 bits
-__device__ __forceinline__ uint32_t even_bits(uint64_t x) {
-    x &= 0x5555555555555555ull;
-    x = (x | (x >> 1)) & 0x3333333333333333ull;
-    x = (x | (x >> 2)) & 0x0F0F0F0F0F0F0F0Full;
-    x = (x | (x >> 4)) & 0x00FF00FF00FF00FFull;
-    x = (x | (x >> 8)) & 0x0000FFFF0000FFFFull;
-    return (uint32_t)(x | (x >> 16));
-}
-
-// One lane per plane word: the 8 row bytes of its 32 samples come out of the
-// (at most three) aligned words that hold them; only words that hold a byte of
-// the row are loaded.
+// One lane per plane word (vcfc_bed::word_planes: the 8 row bytes of its 32
+// samples).
 __global__ __launch_bounds__(256) void k_ld_planes(VcfcLdArgs a) {
     const uint64_t rows = a.state[0], P = a.plane_words;
     const uint32_t S = (uint32_t)a.S, rb = (S + 3u) >> 2, nw = (S + 31u) >> 5;
@@ -82,21 +72,7 @@ __global__ __launch_bounds__(256) void k_ld_planes(VcfcLdArgs a) {
         const uint32_t w = (uint32_t)(e % P);
         uint32_t H = 0, B = 0, V = 0;
         if (w < nw) {
-            const uint8_t *p = a.bed + r * a.row_stride + 8ull * w;
-            const uint32_t nb = ld_min(8u, rb - 8u * w);           // the row's bytes behind p
-            const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 3u);
-            const uint32_t *q = reinterpret_cast<const uint32_t *>(p - sh);
-            const uint32_t d0 = q[0];
-            const uint32_t d1 = sh + nb > 4u ? q[1] : 0u;
-            const uint32_t d2 = sh + nb > 8u ? q[2] : 0u;
-            uint64_t x = (uint64_t)vw::alignbyte(d1, d0, sh) | ((uint64_t)vw::alignbyte(d2, d1, sh) << 32);
-            if (nb < 8u) x &= (1ull << (8u * nb)) - 1ull;
-            const uint32_t lo = even_bits(x), hi = even_bits(x >> 1);
-            const uint32_t left = S - 32u * w;                     // columns of the word that exist
-            const uint32_t m = left >= 32u ? ~0u : (1u << left) - 1u;
-            H = hi & ~lo & m;
-            B = ~hi & ~lo & m;
-            V = (hi | ~lo) & m;
+            vcfc_bed::word_planes(a.bed + r * a.row_stride + 8ull * w, w, S, rb, H, B, V);
         }
         uint32_t *o = a.planes + 3ull * r * P + w;
         o[0] = H;

@@ -65,6 +65,8 @@ EXPORTS = [
     "vcfc_export_bed_regions_file",
     "vcfc_ld_workspace_size", "vcfc_ld_tables_device", "vcfc_ld_window_device", "vcfc_ld_window_buffer",
     "vcfc_ld_window_regions_buffer", "vcfc_ld_window_file", "vcfc_ld_window_regions_file",
+    "vcfc_kin_workspace_size", "vcfc_kin_tables_device", "vcfc_kin_records_device", "vcfc_kinship_buffer",
+    "vcfc_kinship_regions_buffer", "vcfc_kinship_file", "vcfc_kinship_regions_file",
     "vcfc_extract_bound", "vcfc_extract_workspace_size", "vcfc_extract_samples_device", "vcfc_extract_buffer",
     "vcfc_extract_file", "vcfc_extract_regions_buffer", "vcfc_extract_regions_file",
 ]
@@ -186,6 +188,17 @@ def lib():
             "vcfc_ld_window_file": [vp, ctypes.c_char_p, ctypes.c_char_p, u64, ctypes.c_double, ctypes.c_int,
                                     ctypes.c_char_p, u64, ctypes.c_int, u64, u64],
             "vcfc_ld_window_regions_file": [vp, ctypes.c_char_p, ctypes.c_char_p, u64, ctypes.c_double, vp, u64],
+            # kinship
+            "vcfc_kin_workspace_size": [u64, u64],
+            "vcfc_kin_tables_device": [vp, u64, u64, u64, vp, u64, ctypes.c_int, vp, u64, vp, vp],
+            "vcfc_kin_records_device": [vp, u64, vp, vp, u64, u64, vp, u64, ctypes.c_int, vp, vp, u64, vp, vp],
+            "vcfc_kinship_buffer": [vp, vp, u64, ctypes.c_int, ctypes.c_char_p, u64, ctypes.c_int, u64, u64, vp, u64, vp, u64,
+                                    ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)],
+            "vcfc_kinship_regions_buffer": [vp, vp, u64, vp, u64, vp, u64, vp, u64, ctypes.POINTER(u64),
+                                            ctypes.POINTER(u64), ctypes.POINTER(u64)],
+            "vcfc_kinship_file": [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_double, ctypes.c_int,
+                                  ctypes.c_char_p, u64, ctypes.c_int, u64, u64],
+            "vcfc_kinship_regions_file": [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_double, vp, u64],
             # extract
             "vcfc_extract_bound": [u64, u64, u64],
             "vcfc_extract_workspace_size": [u64, u64],
@@ -204,7 +217,7 @@ def lib():
                  "vcfc_counts_lds_samples", "vcfc_regions_workspace_size", "vcfc_matrix_row_bytes",
                  "vcfc_matrix_lds_samples", "vcfc_matrix_workspace_size", "vcfc_extract_bound",
                  "vcfc_extract_workspace_size", "vcfc_counts_trip_records", "vcfc_matrix_trip_records",
-                 "vcfc_ld_workspace_size"):
+                 "vcfc_ld_workspace_size", "vcfc_kin_workspace_size"):
         if hasattr(L, name):
             getattr(L, name).restype = u64
     L.vcfc_record_hash_device.argtypes = [vp, vp, u64, vp, vp]
@@ -825,6 +838,69 @@ class Context:
             int(query.has_range) if query is not None else 0, query.start if query is not None else 0,
             query.end if query is not None else 0))
 
+    def kinship_buffer(self, data, query=None, regions=None):
+        """kinship over .vcfc bytes: the 3 x 3 genotype tables
+        of every pair of samples over the rows of genotype_matrix_buffer
+        (every record, or those matching `query` or `regions`).  Returns
+        (status, record_indices, tables uint32[S, S, 3, 3]): tables[i, j, a, b]
+        = the rows with genotype a in sample i and b in sample j, both called.
+        On VCFC_E_FORMAT the square is that of the rows before the failing
+        record (`last_kinship_record`: its file index); any other failure
+        returns an empty square.  kinship_stats(tables) gives the statistics."""
+        if query is not None and regions is not None:
+            raise ValueError("query and regions exclude each other")
+        if query is not None and not isinstance(query, VcfCoordinateQuery):
+            query = parse_coordinate_string(query)
+        src = np.frombuffer(data, dtype=np.uint8)
+        tab = np.frombuffer(_regions_table(regions), dtype=np.uint8) if regions is not None else None
+        ref = query.reference_name if query is not None else b""
+        # sized from the '#CHROM' line and the least record size; a short guess is reported and tried again
+        raw = data if isinstance(data, (bytes, bytearray)) else src.tobytes()
+        at = 0 if raw[:6] == b"#CHROM" else raw.find(b"\n#CHROM") + 1
+        eol = raw.find(b"\n", at)
+        S0 = max(0, raw[at:eol].count(b"\t") - 8) if eol > 0 else 0
+        cap, tcap = len(data) // 12 + 16, S0 * S0
+        while True:
+            idx, tables = np.zeros(max(cap, 1), dtype=np.uint64), np.zeros(max(tcap, 1) * 9, dtype=np.uint32)
+            n, S, bad = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+            if tab is not None:
+                st = _need("vcfc_kinship_regions_buffer")(
+                    self._h, src.ctypes.data, len(data), tab.ctypes.data, len(tab), idx.ctypes.data, cap,
+                    tables.ctypes.data, tcap, ctypes.byref(n), ctypes.byref(S), ctypes.byref(bad))
+            else:
+                st = _need("vcfc_kinship_buffer")(
+                    self._h, src.ctypes.data, len(data), int(query is not None), ref, len(ref),
+                    int(query.has_range) if query is not None else 0, query.start if query is not None else 0,
+                    query.end if query is not None else 0, idx.ctypes.data, cap, tables.ctypes.data, tcap,
+                    ctypes.byref(n), ctypes.byref(S), ctypes.byref(bad))
+            if st == E_NOSPACE and (n.value > cap or S.value * S.value > tcap):
+                cap, tcap = n.value, S.value * S.value
+                continue
+            self.last_kinship_record = bad.value
+            if st not in (OK, E_FORMAT) or S.value * S.value > tcap:
+                return st, idx[:0].copy(), np.zeros((0, 0, 3, 3), dtype=np.uint32)
+            return st, idx[:n.value].copy(), tables[:S.value * S.value * 9].reshape(S.value, S.value, 3, 3).copy()
+
+    def kinship_file(self, in_path, out_tsv, min_kinship=None, query=None, regions=None):
+        """As `main kinship <in.vcfc> <out.tsv> <min-kinship|all> [<query>]` or,
+        with `regions`, `main kinship-regions`: one text line per pair of
+        samples (min_kinship None: every pair)."""
+        if query is not None and regions is not None:
+            raise ValueError("query and regions exclude each other")
+        has_min, m = int(min_kinship is not None), float(min_kinship or 0.0)
+        if regions is not None:
+            tab = np.frombuffer(_regions_table(regions), dtype=np.uint8)
+            raise_for(_need("vcfc_kinship_regions_file")(self._h, in_path.encode(), out_tsv.encode(), has_min, m,
+                                                         tab.ctypes.data, len(tab)))
+            return
+        if query is not None and not isinstance(query, VcfCoordinateQuery):
+            query = parse_coordinate_string(query)
+        ref = query.reference_name if query is not None else b""
+        raise_for(_need("vcfc_kinship_file")(
+            self._h, in_path.encode(), out_tsv.encode(), has_min, m, int(query is not None), ref, len(ref),
+            int(query.has_range) if query is not None else 0, query.start if query is not None else 0,
+            query.end if query is not None else 0))
+
     def extract_buffer(self, data, cols=None, query=None, regions=None, cap=None):
         """extract: the 0-based sample columns `cols` (None:
         all) of the records `query` or `regions` match (neither: all), as a
@@ -1395,3 +1471,47 @@ def ld_r2(tables):
     c = cov.astype(np.float64)
     den = np.where(ok, vx.astype(np.float64) * vy.astype(np.float64), 1.0)
     return np.where(ok, (c * c) / den, np.nan)
+
+
+def kin_workspace_size(n_records, samples):
+    return int(_need("vcfc_kin_workspace_size")(n_records, samples))
+
+
+def kin_tables_device(d_bed, n_rows, row_stride, samples, d_tables, tables_cap, accumulate, d_ws, ws_bytes, d_err, stream=0):
+    """The genotype tables of every pair of samples over device-resident .bed
+    rows (include/vcfc.h vcfc_kin_tables_device): table (i, j) at d_tables +
+    (i * samples + j) * 9 uint32; accumulate != 0 adds to what d_tables holds.
+    Asynchronous on `stream`."""
+    return _need("vcfc_kin_tables_device")(d_bed, n_rows, row_stride, samples, d_tables, tables_cap, accumulate, d_ws,
+                                           ws_bytes, d_err, stream)
+
+
+def kin_records_device(d_in, in_bytes, d_rec_start, d_select, n, samples, d_tables, tables_cap, accumulate, d_row_of, d_ws,
+                       ws_bytes, d_err, stream=0):
+    """The composed call on device-resident records (include/vcfc.h
+    vcfc_kin_records_device): .bed rows into the workspace, sample-major bit
+    planes, pairs; d_row_of[n] = the rows.  Asynchronous on `stream`,
+    capturable."""
+    return _need("vcfc_kin_records_device")(d_in, in_bytes, d_rec_start, d_select, n, samples, d_tables, tables_cap,
+                                            accumulate, d_row_of, d_ws, ws_bytes, d_err, stream)
+
+
+def kinship_stats(tables):
+    """(N, IBS0, IBS1, IBS2, DST, KINSHIP) of genotype tables (any shape ending
+    in 3, 3, or in 9): int64 arrays, and float64 with nan where
+    undefined (DST: N == 0; KINSHIP, the KING-robust between-family estimator:
+    min(HET_A, HET_B) == 0).  Integers exact in int64, then one conversion per
+    operand and one division, as the C library's text output."""
+    t = np.asarray(tables).astype(np.int64)
+    t = t.reshape(t.shape[:-2] + (9,)) if t.shape[-1] == 3 else t
+    N = t.sum(axis=-1)
+    ibs0 = t[..., 2] + t[..., 6]
+    ibs2 = t[..., 0] + t[..., 4] + t[..., 8]
+    ibs1 = N - ibs0 - ibs2
+    hh = t[..., 4]
+    het_a, het_b = t[..., 3] + hh + t[..., 5], t[..., 1] + hh + t[..., 7]
+    m = np.minimum(het_a, het_b)
+    dst = np.where(N != 0, (2 * ibs2 + ibs1).astype(np.float64) / np.where(N != 0, 2 * N, 1).astype(np.float64), np.nan)
+    num = 2 * hh - 4 * ibs0 + 2 * m - het_a - het_b
+    kin = np.where(m != 0, num.astype(np.float64) / np.where(m != 0, 4 * m, 1).astype(np.float64), np.nan)
+    return N, ibs0, ibs1, ibs2, dst, kin
